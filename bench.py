@@ -9,7 +9,10 @@ decode kernel, ending with the library's own stream sync.  Multi-GPU: one
 process per GPU, each decodes its own shard (weak scaling) and the
 per-template processed counts are all-gathered over RCCL after every step.
 
-Prints ONE JSON line (rank 0).
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times --steps
+steps and prints the line; --dump-outputs DIR also writes what the last timed
+step returned (dump_outputs), and --full adds the legs the headline figure
+does not need (the cpu_baseline).
 """
 import argparse
 import json
@@ -130,6 +133,60 @@ def committed_agg_traffic(key, workload):
     return best
 
 
+DUMP_SEED = 0x4E475A44
+DUMP_BLOCK = 256               # rows per sampled block
+DUMP_COLUMN_VALUES = 8 << 20   # float32 values over all column files (32 MiB)
+DUMP_TABLE_ROWS = 1 << 16      # sampled datagram headers / data sets (32 and 16 values a row: 12 MiB)
+
+
+def sample_rows(n, rows, rng):
+    """Sorted row blocks [(first, count)] of [0, n): every row when n <= rows, else blocks of
+    DUMP_BLOCK rows, the first and the last block of the range and seeded ones between them."""
+    if n <= rows:
+        return [(0, n)] if n else []
+    nb = max(2, rows // DUMP_BLOCK)
+    last = (n - 1) // DUMP_BLOCK
+    picks = {0, last} | {int(b) for b in rng.integers(1, max(2, last), nb - 2)}
+    return [(b * DUMP_BLOCK, min(DUMP_BLOCK, n - b * DUMP_BLOCK)) for b in sorted(picks)]
+
+
+def dump_outputs(batch, out_dir, prefix=""):
+    """What the decode call returned, as float32 .npy files (every value a byte, exact in float32):
+    per slot and field the column bytes of a fixed, seeded sample of rows (the same rows for every
+    field of a slot; the float64 `_rows` files name them), the datagram headers and the data sets
+    (sampled the same way), and the record count of every slot.  Under 50 MB for any workload."""
+    import numpy as np
+    from netgauze_amd._lib import d2h
+    os.makedirs(out_dir, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+
+    def save(name, a, dtype=np.float32):
+        np.save(os.path.join(out_dir, prefix + name + ".npy"), np.ascontiguousarray(a, dtype=dtype))
+
+    def row_ids(blocks):
+        return np.concatenate([np.arange(r0, r0 + k) for r0, k in blocks] or [np.zeros(0)])
+
+    def gather(ptr, width, blocks):
+        return np.concatenate([d2h(ptr + r0 * width, k * width).reshape(k, width) for r0, k in blocks]) \
+            if blocks else np.zeros((0, width), dtype=np.uint8)
+
+    slots = batch.slots
+    save("slot_records", [[s.template_id, s.proto, s.n_records] for s in slots], np.float64)
+    live = [s for s in slots if s.n_records]
+    for s in live:
+        row_bytes = sum(f.width for f in s.fields)
+        blocks = sample_rows(s.n_records, DUMP_COLUMN_VALUES // (len(live) * max(1, row_bytes)), rng)
+        name = "slot%02d_p%d_t%d" % (s.index, s.proto, s.template_id)
+        save(name + "_rows", row_ids(blocks), np.float64)
+        for j, f in enumerate(s.fields):
+            save("%s_f%03d_ie%d_%d" % (name, j, f.pen, f.ie_id), gather(s.column_ptr(j), f.width, blocks))
+    for name, ptr, n, width in (("dgram_headers", batch.out.dgrams, batch.n_dgrams, 32),
+                                ("sets", batch.out.sets, batch.n_sets, 16)):
+        blocks = sample_rows(n, DUMP_TABLE_ROWS, rng)
+        save(name + "_rows", row_ids(blocks), np.float64)
+        save(name, gather(ptr, width, blocks))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -142,7 +199,13 @@ def main():
                          "templates (40-153 B) in interleaved messages; cfg4: config 4, NetFlow v9 + IPFIX "
                          "variable-length/enterprise IEs; cfg5: config 5, 16 templates (config 3 + 8 width "
                          "permutations), one shard per GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also what the headline figure does not need: the cpu_baseline leg (the reference "
+                         "algorithm's C restatement timed on this host's cores, ~15 s)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the cpu_baseline leg out")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (a fixed, seeded sample of every "
+                         "slot's columns, the datagram headers and the data sets) as float32 DIR/<name>.npy")
     ap.add_argument("--split", action="store_true",
                     help="split framing (NGZ_OPT_SPLIT: variable-length record walks on a second stream)")
     ap.add_argument("--place-probe", type=int, choices=[0, 1, 2], default=0,
@@ -166,6 +229,10 @@ def main():
                          "(~1 group per record); 7 aggregated fields")
     ap.add_argument("--agg-max-peers", type=int, default=256, help="--agg: the aggregator's max_peers")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.agg or args.e2e or args.contexts > 1):
+        ap.error("--dump-outputs writes the decode step's batch: not with --agg, --e2e or --contexts")
     if args.agg:
         return main_agg(args)
     if args.records is None:
@@ -269,7 +336,7 @@ def main():
     t0 = time.perf_counter()
     if P == 1:
         for _ in range(args.steps):
-            step()
+            b = step()
             dec_ms.append(codec.last_timing()[0])
     elif args.submit:
         # one host thread: step k goes to context k % P once that context's previous batch is collected
@@ -374,7 +441,9 @@ def main():
                      "alg_bytes_per_launch": alg_bytes,
                      "read_gbps": read_bytes / (dec_avg * 1e-3) / 1e9, **(placement or {})},
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.dump_outputs:
+        dump_outputs(b, args.dump_outputs, prefix="rank%d_" % rank if world > 1 else "")
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args.workload)
     if rank == 0:
         print(json.dumps(out), flush=True)

@@ -13,7 +13,7 @@ for W in ${WORKLOADS:-t20}; do
   RV=RECORDS_$W
   ARGS="--workload $W ${!RV:+--records ${!RV}} --steps 20 --warmup 5"
   echo "== $W: bench.py $ARGS"
-  timeout -k 10 600 python bench.py $ARGS > $OUT/bench.json 2> $OUT/bench.err || { tail -20 $OUT/bench.err; exit 2; }
+  timeout -k 10 600 python bench.py $ARGS --full > $OUT/bench.json 2> $OUT/bench.err || { tail -20 $OUT/bench.err; exit 2; }
   cat $OUT/bench.json
   timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o run -- python3 bench.py $ARGS --no-cpu-baseline > $OUT/trace_bench.json 2> $OUT/trace.err || { tail -20 $OUT/trace.err; exit 3; }
   for C in FETCH_SIZE WRITE_SIZE; do

@@ -10,7 +10,7 @@ OUT=gpurun_out/$TAG
 mkdir -p $OUT
 timeout -k 10 900 python -u -m pytest tests/ -q -m gpu -x --timeout 120 --timeout-method thread > $OUT/pytest_gpu.log 2>&1 || { tail -30 $OUT/pytest_gpu.log; exit 1; }
 tail -2 $OUT/pytest_gpu.log
-timeout -k 10 600 python bench.py > $OUT/bench.json 2> $OUT/bench.err || exit 2
+timeout -k 10 600 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err || exit 2
 cat $OUT/bench.json
 timeout -k 10 300 python bench.py --e2e --records 10000000 --steps 5 --warmup 1 > $OUT/e2e_1e7.json 2> $OUT/e2e.err || exit 3
 cat $OUT/e2e_1e7.json
