@@ -64,6 +64,15 @@ AGG_FUNCTIONS = [
     "ngz_agg_key_info", "ngz_agg_value_info", "ngz_agg_flowinfo_json", "ngz_agg_last_timing", "ngz_agg_peer", "ngz_agg_last_path",
     "ngz_agg_abi_version", "ngz_agg_row_bytes", "ngz_agg_set_option",
 ]
+# include/ngz/flow_renormalize.h
+RENORM_FUNCTIONS = [
+    "ngz_renorm_abi_version", "ngz_renorm_create", "ngz_renorm_destroy", "ngz_renorm_last_error", "ngz_renorm_apply",
+    "ngz_renorm_totals", "ngz_renorm_flags", "ngz_renorm_batch_json", "ngz_renorm_last_timing",
+    "ngz_renorm_template_plan",
+]
+NGZ_RENORM_ABI_VERSION = 1
+NGZ_RENORM_OPTIONS = 0x100
+NGZ_E_INVALID, NGZ_E_DEVICE, NGZ_E_NOMEM, NGZ_E_LIMIT = -1, -2, -3, -4
 NGZ_AGG_KEY, NGZ_AGG_ADD, NGZ_AGG_MIN, NGZ_AGG_MAX, NGZ_AGG_OR = range(5)
 NGZ_AGG_E_OVERFLOW, NGZ_AGG_E_COLLISION, NGZ_AGG_E_POISONED = -10, -11, -12
 NGZ_AGG_OPT_LOWCARD, NGZ_AGG_OPT_PARTITION, NGZ_AGG_OPT_OWNER, NGZ_AGG_OPT_HASH_BITS = 1, 2, 3, 4
@@ -180,6 +189,25 @@ class Peer(ctypes.Structure):
 
 
 assert ctypes.sizeof(Peer) == 20
+
+
+class RenormStats(ctypes.Structure):
+    """ngz_renorm_stats: RenormalizationStats plus records_dropped."""
+    _fields_ = [("flows_processed", ctypes.c_uint64), ("flows_renormalized", ctypes.c_uint64),
+                ("ie_missing_or_invalid", ctypes.c_uint64), ("sampling_algorithm_inferred", ctypes.c_uint64),
+                ("records_dropped", ctypes.c_uint64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class RenormPlan(ctypes.Structure):
+    """ngz_renorm_plan (ngz_renorm_template_plan)."""
+    _fields_ = [("param_field", ctypes.c_int16 * 10), ("n_counts", ctypes.c_uint16),
+                ("count_field", ctypes.c_uint16 * 64), ("dropped", ctypes.c_uint8), ("launches", ctypes.c_uint8)]
+
+
+assert ctypes.sizeof(RenormStats) == 40 and ctypes.sizeof(RenormPlan) == 152
 
 AGG_ROW_DTYPE = np.dtype([("window_start", "<u4"), ("flow_type", "u1"), ("reserved0", "u1"), ("peer", "<u2"),
                           ("key_present", "<u4"), ("val_present", "<u4"), ("record_count", "<u8"),
@@ -317,6 +345,29 @@ def load():
     lib.ngz_agg_last_path.restype = ctypes.c_char_p
     lib.ngz_agg_set_option.argtypes = [P, I, ctypes.c_int64]
     lib.ngz_agg_set_option.restype = I
+    # renormalization (flow_renormalize.h)
+    lib.ngz_renorm_abi_version.argtypes, lib.ngz_renorm_abi_version.restype = [], I
+    if lib.ngz_renorm_abi_version() != NGZ_RENORM_ABI_VERSION:
+        raise RuntimeError("netgauze_amd: %s has renormalization ABI version %d, this binding needs %d -- rebuild it"
+                           % (LIB_PATH, lib.ngz_renorm_abi_version(), NGZ_RENORM_ABI_VERSION))
+    lib.ngz_renorm_create.argtypes = [I, ctypes.POINTER(P)]
+    lib.ngz_renorm_create.restype = I
+    lib.ngz_renorm_destroy.argtypes = [P]
+    lib.ngz_renorm_destroy.restype = None
+    lib.ngz_renorm_last_error.argtypes = [P]
+    lib.ngz_renorm_last_error.restype = ctypes.c_char_p
+    lib.ngz_renorm_apply.argtypes = [P, P, ctypes.POINTER(BatchOut), ctypes.POINTER(RenormStats), P]
+    lib.ngz_renorm_apply.restype = I
+    lib.ngz_renorm_totals.argtypes = [P, ctypes.POINTER(RenormStats), I]
+    lib.ngz_renorm_totals.restype = I
+    lib.ngz_renorm_flags.argtypes = [P, U32, ctypes.POINTER(P), ctypes.POINTER(U32)]
+    lib.ngz_renorm_flags.restype = I
+    lib.ngz_renorm_batch_json.argtypes = [P, P, P, JSON_LINE_FN, P]
+    lib.ngz_renorm_batch_json.restype = ctypes.c_int64
+    lib.ngz_renorm_last_timing.argtypes = [P, ctypes.POINTER(ctypes.c_float)]
+    lib.ngz_renorm_last_timing.restype = I
+    lib.ngz_renorm_template_plan.argtypes = [P, ctypes.c_size_t, I, ctypes.POINTER(RenormPlan)]
+    lib.ngz_renorm_template_plan.restype = I
     # ingest (flow_ingest.h)
     lib.ngz_pcap_open.argtypes = [ctypes.c_char_p, ctypes.POINTER(P)]
     lib.ngz_pcap_open.restype = I

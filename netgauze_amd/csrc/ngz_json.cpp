@@ -20,6 +20,7 @@
 #include <cstring>
 
 #include "ngz_host.h"
+#include "ngz_renorm_internal.h"
 
 using namespace ngzh;
 
@@ -396,6 +397,11 @@ int json_view_load(ngz_ctx *ctx, const uint8_t *host_bytes, JsonView &v) {
 }
 
 int json_render(ngz_ctx *ctx, const JsonView &v, uint32_t d, std::string &o, uint32_t *consumed) {
+    return json_render_mode(ctx, v, d, o, consumed, nullptr);
+}
+
+int json_render_mode(ngz_ctx *ctx, const JsonView &v, uint32_t d, std::string &o, uint32_t *consumed,
+                     const RenormJson *mode) {
     const ngz_dgram_hdr &h = v.hdr[d];
     const uint8_t *p = v.bytes + v.offs[d];
     const uint32_t dl = v.lens[d];
@@ -438,6 +444,11 @@ int json_render(ngz_ctx *ctx, const JsonView &v, uint32_t d, std::string &o, uin
     bool first = true;
     while (ds < de || ts < te) {
         const bool take_t = ts < te && (ds >= de || ctx->tmpl_sets[ts].set_pos < v.sets[ds].set_pos);
+        if (take_t && mode) {  // renormalize() filters (options) template sets out (logic.rs:434-449, 497-512)
+            const TemplateSetJson &t = ctx->tmpl_sets[ts++];
+            end = std::max(end, t.set_pos + rd16(p + t.set_pos + 2));
+            continue;
+        }
         if (!first) o += ',';
         first = false;
         if (take_t) {
@@ -454,7 +465,10 @@ int json_render(ngz_ctx *ctx, const JsonView &v, uint32_t d, std::string &o, uin
         o += "{\"Data\":{\"id\":"; put_u64(o, ver_t.tid);
         o += ",\"records\":[";
         const uint32_t nf = (uint32_t)ver_t.specs.size();
-        for (uint32_t r = 0; r < si.n; ++r) {
+        // renormalized mode: records with scope fields are filtered out (logic.rs:415, 484)
+        const uint32_t n_rec = mode && ver_t.n_scope ? 0 : si.n;
+        const uint8_t *flags = mode ? mode->slot_flags[si.slot] : nullptr;
+        for (uint32_t r = 0; r < n_rec; ++r) {
             const uint64_t row = (uint64_t)si.rec0 + r;
             o += r ? ",{\"scope_fields\":[" : "{\"scope_fields\":[";
             for (uint32_t f = 0; f < nf; ++f) {
@@ -464,6 +478,8 @@ int json_render(ngz_ctx *ctx, const JsonView &v, uint32_t d, std::string &o, uin
                 put_field(o, ver_t.specs[f], fd, cols + (uint64_t)cap * fd.col_off + row * fd.width, v.bytes);
             }
             if (ver_t.n_scope == nf) o += "],\"fields\":[";
+            if (flags && (flags[row] & 1))  // logic.rs:371-374
+                o += nf > ver_t.n_scope ? ",{\"NetGauze\":{\"isRenormalized\":true}}" : "{\"NetGauze\":{\"isRenormalized\":true}}";
             o += "]}";
         }
         o += "]}}";

@@ -1,0 +1,548 @@
+// Flow renormalization (include/ngz/flow_renormalize.h): the reference's renormalize()
+// (crates/collector/src/flow/renormalization/logic.rs:381-524) applied in place to the decoded
+// columns of a batch.  One plan-driven streaming kernel per template slot that carries a
+// sampling IE: lanes map to consecutive rows (four per lane), every column access is a
+// coalesced vector load / store; the per-record arithmetic is ngz_renorm_math.h.
+#include <hip/hip_runtime.h>
+
+#include <cstring>
+#include <map>
+#include <string>
+#include <vector>
+
+#include "ngz/flow_renormalize.h"
+#include "ngz_host.h"
+#include "ngz_renorm_internal.h"
+#include "ngz_renorm_math.h"
+
+namespace {
+
+constexpr uint32_t RN_THREADS = 256;
+constexpr uint32_t RN_ROWS_PER_LANE = 4;
+constexpr uint32_t RN_STATS = 3;  // device counters: renormalized, missing_or_invalid, inferred
+
+// What the kernel needs of one slot, passed by value
+struct RnPlan {
+    const uint8_t *param[NGZ_RN_NPARAMS];  // column of the parameter's last occurrence, or null
+    uint64_t *count[NGZ_RENORM_MAX_COUNTS];
+    uint32_t n_counts;
+    uint32_t present;            // bit i: parameter i is in the template
+    uint32_t n_rows;             // the slot's n_records
+    uint32_t reserved;
+    uint8_t *flags;              // one byte per row (room for a whole last quad)
+    const uint32_t *bad;         // one bit per row: row of a message that did not decode
+    unsigned long long *stats;   // [RN_STATS]
+};
+
+// IE -> parameter index, its column width (field_rule's for the IE's data type), or -1
+int param_index(uint16_t ie, uint16_t *width) {
+    static const struct { uint16_t ie, w; } T[NGZ_RN_NPARAMS] = {{34, 4}, {35, 1}, {49, 1}, {50, 4}, {304, 2},
+                                                                 {305, 4}, {306, 4}, {309, 4}, {310, 4}, {311, 8}};
+    for (int i = 0; i < NGZ_RN_NPARAMS; ++i)
+        if (T[i].ie == ie) { *width = T[i].w; return i; }
+    return -1;
+}
+bool is_count_ie(uint16_t ie) { return ie == 1 || ie == 2 || ie == 85 || ie == 86; }
+
+__device__ __forceinline__ uint64_t rn_wave_sum(uint64_t v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+    return v;
+}
+
+// four consecutive rows of a 1-, 2- or 4-byte column (r0 a multiple of 4: one aligned vector load)
+__device__ __forceinline__ void rn_load4(const uint8_t *col, uint32_t w, uint32_t r0, uint32_t v[4]) {
+    if (w == 4) {
+        const uint4 x = *(const uint4 *)(col + 4ull * r0);
+        v[0] = x.x; v[1] = x.y; v[2] = x.z; v[3] = x.w;
+    } else if (w == 2) {
+        const uint2 x = *(const uint2 *)(col + 2ull * r0);
+        v[0] = x.x & 0xFFFFu; v[1] = x.x >> 16; v[2] = x.y & 0xFFFFu; v[3] = x.y >> 16;
+    } else {
+        const uint32_t x = *(const uint32_t *)(col + r0);
+        v[0] = x & 0xFFu; v[1] = (x >> 8) & 0xFFu; v[2] = (x >> 16) & 0xFFu; v[3] = x >> 24;
+    }
+}
+
+// Bit masks of the parameters by column width
+constexpr uint32_t RN_W1 = (1u << NGZ_RN_P35) | (1u << NGZ_RN_P49);
+constexpr uint32_t RN_W2 = 1u << NGZ_RN_P304;
+
+__global__ __launch_bounds__(RN_THREADS) void k_renorm(const RnPlan P) {
+    __shared__ unsigned long long acc[RN_STATS];
+    if (threadIdx.x < RN_STATS) acc[threadIdx.x] = 0;
+    __syncthreads();
+    uint32_t n_renorm = 0, n_invalid = 0, n_inferred = 0;
+    const uint32_t quads = (P.n_rows + RN_ROWS_PER_LANE - 1) / RN_ROWS_PER_LANE;
+    for (uint32_t q = blockIdx.x * RN_THREADS + threadIdx.x; q < quads; q += gridDim.x * RN_THREADS) {
+        const uint32_t r0 = q * RN_ROWS_PER_LANE;
+        // rows of this quad that are records of a decoded message (r0 % 4 == 0: one bitmap word)
+        uint32_t live = ~(P.bad[r0 >> 5] >> (r0 & 31)) & 0xFu;
+        if (P.n_rows - r0 < RN_ROWS_PER_LANE) live &= (1u << (P.n_rows - r0)) - 1u;
+        NgzRenormParams prm[RN_ROWS_PER_LANE];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            prm[j] = NgzRenormParams{};
+            prm[j].present = P.present;
+        }
+        // a quad's loads stay inside the column: the capacity is a multiple of 4 rows
+#define RN_PARAM(IDX, MEMBER)                                                                       \
+    if (P.present & (1u << (IDX))) {                                                                \
+        uint32_t v[4];                                                                              \
+        rn_load4(P.param[IDX], ((1u << (IDX)) & RN_W1) ? 1u : ((1u << (IDX)) & RN_W2) ? 2u : 4u, r0, v); \
+        prm[0].MEMBER = v[0]; prm[1].MEMBER = v[1]; prm[2].MEMBER = v[2]; prm[3].MEMBER = v[3];      \
+    }
+        RN_PARAM(NGZ_RN_P34, interval34)
+        RN_PARAM(NGZ_RN_P35, algorithm35)
+        RN_PARAM(NGZ_RN_P49, mode49)
+        RN_PARAM(NGZ_RN_P50, interval50)
+        RN_PARAM(NGZ_RN_P304, selector304)
+        RN_PARAM(NGZ_RN_P305, interval305)
+        RN_PARAM(NGZ_RN_P306, space306)
+        RN_PARAM(NGZ_RN_P309, size309)
+        RN_PARAM(NGZ_RN_P310, population310)
+#undef RN_PARAM
+        if (P.present & (1u << NGZ_RN_P311)) {
+            const double2 a = *(const double2 *)(P.param[NGZ_RN_P311] + 8ull * r0);
+            const double2 b = *(const double2 *)(P.param[NGZ_RN_P311] + 8ull * r0 + 16);
+            prm[0].probability311 = a.x; prm[1].probability311 = a.y;
+            prm[2].probability311 = b.x; prm[3].probability311 = b.y;
+        }
+        double k[RN_ROWS_PER_LANE];
+        uint32_t scale = 0;  // rows with a factor
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const NgzRenormFactor f = ngz_renorm_factor(prm[j]);
+            k[j] = f.k;
+            if ((live >> j) & 1u) {
+                n_invalid += f.invalid;
+                n_inferred += f.inferred;
+                if (f.has_k) scale |= 1u << j;
+            }
+        }
+        const bool whole = P.n_rows - r0 >= RN_ROWS_PER_LANE;
+        if (scale) {
+            for (uint32_t c = 0; c < P.n_counts; ++c) {
+                uint64_t *col = P.count[c] + r0;
+                if (whole) {
+                    ulonglong2 a = *(const ulonglong2 *)col, b = *(const ulonglong2 *)(col + 2);
+                    if (scale & 1u) a.x = ngz_renorm_scale(a.x, k[0]);
+                    if (scale & 2u) a.y = ngz_renorm_scale(a.y, k[1]);
+                    if (scale & 4u) b.x = ngz_renorm_scale(b.x, k[2]);
+                    if (scale & 8u) b.y = ngz_renorm_scale(b.y, k[3]);
+                    *(ulonglong2 *)col = a;
+                    *(ulonglong2 *)(col + 2) = b;
+                } else {  // the slot's last rows: nothing past n_rows is written
+#pragma unroll
+                    for (int j = 0; j < 3; ++j)
+                        if ((scale >> j) & 1u) col[j] = ngz_renorm_scale(col[j], k[j]);
+                }
+            }
+        }
+        const uint32_t flagged = P.n_counts ? scale : 0u;
+        n_renorm += __popc(flagged);
+        // the flags of four rows in one dword store
+        *(uint32_t *)(P.flags + r0) = (flagged & 1u) | ((flagged & 2u) << 7) | ((flagged & 4u) << 14) | ((flagged & 8u) << 21);
+    }
+    const uint64_t s0 = rn_wave_sum(n_renorm), s1 = rn_wave_sum(n_invalid), s2 = rn_wave_sum(n_inferred);
+    if ((threadIdx.x & 63) == 0) {
+        if (s0) atomicAdd(&acc[0], (unsigned long long)s0);
+        if (s1) atomicAdd(&acc[1], (unsigned long long)s1);
+        if (s2) atomicAdd(&acc[2], (unsigned long long)s2);
+    }
+    __syncthreads();
+    if (threadIdx.x < RN_STATS && acc[threadIdx.x]) atomicAdd(&P.stats[threadIdx.x], acc[threadIdx.x]);
+}
+
+// Rows of messages that did not decode (the final status is on the device after decode, k_counts;
+// the aggregation push selects rows by datagram the same way): one thread per data set marks its
+// rows in the slot's bitmap and counts them.  err bit 0: a set outside the batch's tables.
+__global__ void k_renorm_sets(const ngz_set_info *__restrict__ sets, uint32_t n_sets, const ngz_dgram_hdr *__restrict__ hdr,
+                              uint32_t n_dgrams, uint32_t n_slots, const uint32_t *__restrict__ slot_rows,
+                              const uint32_t *__restrict__ bm_off, uint32_t *__restrict__ bitmap,
+                              unsigned long long *__restrict__ bad_rows, unsigned int *__restrict__ err) {
+    for (uint32_t s = blockIdx.x * blockDim.x + threadIdx.x; s < n_sets; s += gridDim.x * blockDim.x) {
+        const ngz_set_info si = sets[s];
+        if (!si.n) continue;
+        if (si.dgram >= n_dgrams || si.slot >= n_slots || (uint64_t)si.rec0 + si.n > slot_rows[si.slot]) {
+            atomicOr(err, 1u);
+            continue;
+        }
+        if (hdr[si.dgram].status == NGZ_DG_OK) continue;
+        atomicAdd(&bad_rows[si.slot], (unsigned long long)si.n);
+        uint32_t *bm = bitmap + bm_off[si.slot];
+        uint32_t r = si.rec0;
+        const uint32_t e = si.rec0 + si.n;
+        while (r < e) {
+            const uint32_t w = r >> 5, lo = r & 31u;
+            const uint32_t hi = (e - (w << 5)) < 32u ? e - (w << 5) : 32u;
+            const uint32_t mask = (hi == 32u ? ~0u : (1u << hi) - 1u) & ~((1u << lo) - 1u);
+            atomicOr(&bm[w], mask);
+            r = (w + 1u) << 5;
+        }
+    }
+}
+
+// One field of a template as the plan builder sees it
+struct PlanField {
+    uint32_t pen;
+    uint16_t ie;
+    bool scope;
+    bool usable;  // decodes into the column the kernel expects (the IE's width, NGZ_K_UINT)
+};
+
+// ngz_renorm_plan of a template's fields (scope first); false: more count fields than the plan holds
+bool build_plan(const std::vector<PlanField> &fields, ngz_renorm_plan *out) {
+    memset(out, 0, sizeof *out);
+    for (int i = 0; i < NGZ_RN_NPARAMS; ++i) out->param_field[i] = -1;
+    bool any_param = false, fits = true;
+    for (size_t i = 0; i < fields.size(); ++i) {
+        const PlanField &f = fields[i];
+        if (f.scope) { out->dropped = 1; continue; }
+        if (f.pen != 0 || !f.usable) continue;
+        uint16_t w;
+        const int pi = param_index(f.ie, &w);
+        if (pi >= 0) {  // the last occurrence wins (logic.rs:327-341)
+            out->param_field[pi] = (int16_t)i;
+            any_param = true;
+        } else if (is_count_ie(f.ie)) {
+            if (out->n_counts < NGZ_RENORM_MAX_COUNTS) out->count_field[out->n_counts++] = (uint16_t)i;
+            else fits = false;
+        }
+    }
+    out->launches = (!out->dropped && any_param) ? 1 : 0;
+    return fits || out->dropped || !any_param;
+}
+
+}  // namespace
+
+struct ngz_renorm {
+    int device = 0;
+    std::string last_error;
+    ngz_renorm_stats totals{};
+    std::map<const ngz_ctx *, uint64_t> applied;  // context -> batch serial last applied
+    // the batch last applied
+    const ngz_ctx *last_ctx = nullptr;
+    uint64_t last_serial = 0;
+    std::vector<uint64_t> flag_off;   // per slot: offset of its flags in d_flags
+    std::vector<uint32_t> slot_rows;  // per slot: n_records
+    ngzh::DevBuf<uint8_t> d_flags;
+    ngzh::DevBuf<uint32_t> d_bitmap;
+    ngzh::DevBuf<uint32_t> d_meta;               // slot_rows[S], bm_off[S]
+    ngzh::DevBuf<unsigned long long> d_counters;  // stats[RN_STATS], err, bad_rows[S]
+    uint32_t *h_meta = nullptr;                   // pinned
+    size_t h_meta_cap = 0;
+    unsigned long long *h_counters = nullptr;     // pinned
+    size_t h_counters_cap = 0;
+    hipEvent_t ev[2]{};
+    float apply_ms = 0;
+    int n_cus = 256;
+};
+
+namespace {
+
+int rfail(ngz_renorm *r, int rc, const std::string &msg) {
+    if (r) r->last_error = msg;
+    return rc;
+}
+
+#define RN_HIP(r, x)                                                                            \
+    do {                                                                                        \
+        hipError_t e_ = (x);                                                                    \
+        if (e_ != hipSuccess) return rfail(r, NGZ_E_DEVICE, std::string(#x) + ": " + hipGetErrorString(e_)); \
+    } while (0)
+
+template <class T>
+int pinned_reserve(T **p, size_t *cap, size_t n) {
+    if (n <= *cap) return 0;
+    if (*p) hipHostFree(*p);
+    *p = nullptr;
+    *cap = 0;
+    if (hipHostMalloc((void **)p, n * sizeof(T), hipHostMallocDefault) != hipSuccess) return -1;
+    *cap = n;
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ngz_renorm_abi_version(void) { return NGZ_RENORM_ABI_VERSION; }
+
+int ngz_renorm_create(int device, ngz_renorm **out) {
+    if (!out) return NGZ_E_INVALID;
+    *out = nullptr;
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || device < 0 || device >= n) return NGZ_E_DEVICE;
+    if (hipSetDevice(device) != hipSuccess) return NGZ_E_DEVICE;
+    ngz_renorm *r = new ngz_renorm;
+    r->device = device;
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0)
+        r->n_cus = prop.multiProcessorCount;
+    if (hipEventCreate(&r->ev[0]) != hipSuccess || hipEventCreate(&r->ev[1]) != hipSuccess) {
+        ngz_renorm_destroy(r);
+        return NGZ_E_DEVICE;
+    }
+    *out = r;
+    return NGZ_OK;
+}
+
+void ngz_renorm_destroy(ngz_renorm *r) {
+    if (!r) return;
+    hipSetDevice(r->device);
+    r->d_flags.release();
+    r->d_bitmap.release();
+    r->d_meta.release();
+    r->d_counters.release();
+    if (r->h_meta) hipHostFree(r->h_meta);
+    if (r->h_counters) hipHostFree(r->h_counters);
+    for (hipEvent_t e : r->ev)
+        if (e) hipEventDestroy(e);
+    delete r;
+}
+
+const char *ngz_renorm_last_error(ngz_renorm *r) { return r ? r->last_error.c_str() : "null renormalizer"; }
+
+int ngz_renorm_apply(ngz_renorm *r, ngz_ctx *ctx, const ngz_batch_out *out, ngz_renorm_stats *batch_stats,
+                     void *hip_stream) {
+    if (!r || !ctx || !out) return NGZ_E_INVALID;
+    if (batch_stats) memset(batch_stats, 0, sizeof *batch_stats);
+    if (ctx->device != r->device) return rfail(r, NGZ_E_INVALID, "the context is on another device");
+    if (ctx->async.pending.load()) return rfail(r, NGZ_E_INVALID, "a submitted decode is pending on the context");
+    {
+        auto it = r->applied.find(ctx);
+        if (it != r->applied.end() && it->second == ctx->batch_serial)
+            return rfail(r, NGZ_E_INVALID, "this batch was already renormalized");
+    }
+    const uint32_t S = out->n_slots, D = out->n_dgrams, NS = out->n_sets;
+    if (S > NGZ_MAX_SLOTS || (S && !out->slots)) return rfail(r, NGZ_E_INVALID, "slot table");
+    RN_HIP(r, hipSetDevice(r->device));
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+
+    // per-slot plans from the slot's column layout; nothing is launched before every slot checked out
+    struct SlotWork {
+        ngz_renorm_plan plan;
+        RnPlan k;
+    };
+    std::vector<SlotWork> work(S);
+    std::vector<ngz_field_info> fi;
+    std::vector<PlanField> pf;
+    std::vector<uint64_t> flag_off(S, 0);
+    std::vector<uint32_t> slot_rows(S, 0), bm_off(S, 0);
+    uint64_t flag_bytes = 0, bm_words = 0;
+    for (uint32_t s = 0; s < S; ++s) {
+        const ngz_slot_info &si = out->slots[s];
+        SlotWork &w = work[s];
+        memset(&w, 0, sizeof w);
+        slot_rows[s] = si.n_records;
+        flag_off[s] = flag_bytes;
+        bm_off[s] = (uint32_t)bm_words;
+        flag_bytes += ((uint64_t)si.n_records + 15) & ~15ull;  // 16-byte aligned, room for a last quad
+        bm_words += ((uint64_t)si.n_records + 31) / 32 + 1;
+        if (!si.n_records) continue;
+        const int nf = ngz_slot_fields(ctx, s, nullptr, 0);
+        if (nf < 0) return rfail(r, NGZ_E_INVALID, "ngz_slot_fields: not the context's last batch");
+        fi.resize(std::max(nf, 1));
+        ngz_slot_fields(ctx, s, fi.data(), (uint32_t)nf);
+        pf.resize(nf);
+        for (int i = 0; i < nf; ++i) {
+            uint16_t pw = 0;
+            const int pi = fi[i].pen == 0 ? param_index(fi[i].ie_id, &pw) : -1;
+            const uint16_t want = pi >= 0 ? pw : 8;
+            pf[i] = PlanField{fi[i].pen, fi[i].ie_id, fi[i].is_scope != 0, fi[i].kind == NGZ_K_UINT && fi[i].width == want};
+        }
+        if (!build_plan(pf, &w.plan))
+            return rfail(r, NGZ_E_LIMIT, "a template with more than 64 count fields");
+        if (!w.plan.launches) continue;
+        if (!si.columns || ((uintptr_t)si.columns & 15) || (si.capacity & 3) || si.capacity < si.n_records)
+            return rfail(r, NGZ_E_LIMIT, "unexpected column block alignment");
+        for (int i = 0; i < NGZ_RN_NPARAMS; ++i) {
+            if (w.plan.param_field[i] < 0) continue;
+            w.k.param[i] = si.columns + (uint64_t)si.capacity * fi[w.plan.param_field[i]].col_off;
+            w.k.present |= 1u << i;
+        }
+        for (uint32_t c = 0; c < w.plan.n_counts; ++c)
+            w.k.count[c] = (uint64_t *)(si.columns + (uint64_t)si.capacity * fi[w.plan.count_field[c]].col_off);
+        w.k.n_counts = w.plan.n_counts;
+        w.k.n_rows = si.n_records;
+    }
+    if (flag_bytes >> 32 || bm_words >> 32) return rfail(r, NGZ_E_LIMIT, "batch too large");
+    const size_t n_counters = RN_STATS + 1 + S;
+    if (r->d_flags.ensure(flag_bytes + 16) || r->d_bitmap.ensure(bm_words + 1) || r->d_meta.ensure(2ull * S + 2) ||
+        r->d_counters.ensure(n_counters) || pinned_reserve(&r->h_meta, &r->h_meta_cap, 2ull * S + 2) ||
+        pinned_reserve(&r->h_counters, &r->h_counters_cap, n_counters))
+        return rfail(r, NGZ_E_NOMEM, "renormalizer buffers");
+    // from here on the batch counts as applied: the columns may change
+    r->applied[ctx] = ctx->batch_serial;
+    r->last_ctx = ctx;
+    r->last_serial = ctx->batch_serial;
+    r->flag_off = flag_off;
+    r->slot_rows = slot_rows;
+    r->apply_ms = 0;
+    ctx->json_view.reset();
+
+    for (uint32_t s = 0; s < S; ++s) {
+        r->h_meta[s] = slot_rows[s];
+        r->h_meta[S + s] = bm_off[s];
+    }
+    RN_HIP(r, hipEventRecord(r->ev[0], st));
+    if (S) RN_HIP(r, hipMemcpyAsync(r->d_meta.p, r->h_meta, 2ull * S * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    RN_HIP(r, hipMemsetAsync(r->d_counters.p, 0, n_counters * sizeof(unsigned long long), st));
+    RN_HIP(r, hipMemsetAsync(r->d_bitmap.p, 0, (bm_words + 1) * sizeof(uint32_t), st));
+    unsigned long long *d_stats = r->d_counters.p, *d_bad = r->d_counters.p + RN_STATS + 1;
+    unsigned int *d_err = (unsigned int *)(r->d_counters.p + RN_STATS);
+    if (NS && D && S) {
+        const uint32_t nb = (uint32_t)std::min<uint64_t>(((uint64_t)NS + 255) / 256, (uint64_t)r->n_cus * 8);
+        hipLaunchKernelGGL(k_renorm_sets, dim3(nb), dim3(256), 0, st, out->sets, NS, out->dgrams, D, S, r->d_meta.p,
+                           r->d_meta.p + S, r->d_bitmap.p, d_bad, d_err);
+        RN_HIP(r, hipGetLastError());
+    }
+    uint32_t launches = 0;
+    for (uint32_t s = 0; s < S; ++s) {
+        SlotWork &w = work[s];
+        if (!slot_rows[s]) continue;
+        uint8_t *flags = r->d_flags.p + flag_off[s];
+        if (!w.plan.launches) {  // its flags read 0
+            RN_HIP(r, hipMemsetAsync(flags, 0, ((uint64_t)slot_rows[s] + 15) & ~15ull, st));
+            continue;
+        }
+        w.k.flags = flags;
+        w.k.bad = r->d_bitmap.p + bm_off[s];
+        w.k.stats = d_stats;
+        const uint64_t quads = ((uint64_t)slot_rows[s] + RN_ROWS_PER_LANE - 1) / RN_ROWS_PER_LANE;
+        const uint32_t nb = (uint32_t)std::min<uint64_t>((quads + RN_THREADS - 1) / RN_THREADS, (uint64_t)r->n_cus * 16);
+        hipLaunchKernelGGL(k_renorm, dim3(nb), dim3(RN_THREADS), 0, st, w.k);
+        RN_HIP(r, hipGetLastError());
+        ++launches;
+    }
+    RN_HIP(r, hipEventRecord(r->ev[1], st));
+    RN_HIP(r, hipMemcpyAsync(r->h_counters, r->d_counters.p, n_counters * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    RN_HIP(r, hipStreamSynchronize(st));
+    if (launches) RN_HIP(r, hipEventElapsedTime(&r->apply_ms, r->ev[0], r->ev[1]));
+    if (r->h_counters[RN_STATS] & 1) return rfail(r, NGZ_E_INVALID, "a data set outside the batch's tables: `out` is not the context's last decode");
+    ngz_renorm_stats bs{};
+    bs.flows_renormalized = r->h_counters[0];
+    bs.ie_missing_or_invalid = r->h_counters[1];
+    bs.sampling_algorithm_inferred = r->h_counters[2];
+    for (uint32_t s = 0; s < S; ++s) {
+        if (!slot_rows[s]) continue;
+        const uint64_t ok_rows = slot_rows[s] - std::min<uint64_t>(slot_rows[s], r->h_counters[RN_STATS + 1 + s]);
+        if (work[s].plan.dropped) bs.records_dropped += ok_rows;
+        else bs.flows_processed += ok_rows;
+    }
+    r->totals.flows_processed += bs.flows_processed;
+    r->totals.flows_renormalized += bs.flows_renormalized;
+    r->totals.ie_missing_or_invalid += bs.ie_missing_or_invalid;
+    r->totals.sampling_algorithm_inferred += bs.sampling_algorithm_inferred;
+    r->totals.records_dropped += bs.records_dropped;
+    if (batch_stats) *batch_stats = bs;
+    return NGZ_OK;
+}
+
+int ngz_renorm_totals(ngz_renorm *r, ngz_renorm_stats *totals, int reset) {
+    if (!r || !totals) return NGZ_E_INVALID;
+    *totals = r->totals;
+    if (reset) r->totals = ngz_renorm_stats{};
+    return NGZ_OK;
+}
+
+int ngz_renorm_flags(ngz_renorm *r, uint32_t slot, const uint8_t **dev_flags, uint32_t *n) {
+    if (!r || !dev_flags || !n) return NGZ_E_INVALID;
+    if (!r->last_ctx || slot >= r->slot_rows.size()) return rfail(r, NGZ_E_INVALID, "no such slot in the batch last applied");
+    *dev_flags = r->d_flags.p + r->flag_off[slot];
+    *n = r->slot_rows[slot];
+    return NGZ_OK;
+}
+
+int64_t ngz_renorm_batch_json(ngz_renorm *r, ngz_ctx *ctx, const uint8_t *host_bytes, ngz_json_line_fn fn, void *user) {
+    if (!r || !ctx || !fn) return NGZ_E_INVALID;
+    if (r->last_ctx != ctx || r->last_serial != ctx->batch_serial || ctx->async.pending.load())
+        return rfail(r, NGZ_E_INVALID, "the context's last batch is not the batch last applied");
+    RN_HIP(r, hipSetDevice(r->device));
+    const size_t S = r->slot_rows.size();
+    if (S != ctx->slot_infos.size()) return rfail(r, NGZ_E_INVALID, "slot table");
+    const uint64_t total = S ? r->flag_off[S - 1] + (((uint64_t)r->slot_rows[S - 1] + 15) & ~15ull) : 0;
+    std::vector<uint8_t> flags(total + 1);
+    if (total) RN_HIP(r, hipMemcpy(flags.data(), r->d_flags.p, total, hipMemcpyDeviceToHost));
+    ngzh::RenormJson mode;
+    mode.slot_flags.assign(S, nullptr);
+    for (size_t s = 0; s < S; ++s)
+        if (r->slot_rows[s]) mode.slot_flags[s] = flags.data() + r->flag_off[s];
+    ngzh::JsonView v;
+    const int rc = ngzh::json_view_load(ctx, host_bytes, v);
+    if (rc) return rfail(r, rc, "json_view_load");
+    int64_t lines = 0;
+    std::string s;
+    for (uint32_t d = 0; d < ctx->last_in.n; ++d) {
+        s.clear();
+        uint32_t consumed = 0;
+        const int st = ngzh::json_render_mode(ctx, v, d, s, &consumed, &mode);
+        if (st < 0) return st;
+        if (st != NGZ_DG_OK && st != NGZ_DG_ERROR) continue;
+        if (fn(user, d, st, s.data(), s.size(), consumed)) break;
+        ++lines;
+    }
+    return lines;
+}
+
+int ngz_renorm_last_timing(ngz_renorm *r, float *apply_ms) {
+    if (!r || !apply_ms) return NGZ_E_INVALID;
+    *apply_ms = r->apply_ms;
+    return NGZ_OK;
+}
+
+int ngz_renorm_template_plan(const uint8_t *tmpl, size_t len, int proto, ngz_renorm_plan *out) {
+    if (!tmpl || !out) return NGZ_E_INVALID;
+    const bool options = (proto & NGZ_RENORM_OPTIONS) != 0;
+    proto &= ~NGZ_RENORM_OPTIONS;
+    if (proto != 10 && proto != 9) return NGZ_E_INVALID;
+    size_t pos = 2;  // template id
+    uint32_t n_fields = 0, n_scope = 0;
+    size_t scope_end = 0, end = len;  // NetFlow v9 options: byte lengths
+    if (!options) {
+        if (len < 4) return NGZ_E_INVALID;
+        n_fields = ngzh::rd16(tmpl + 2);
+        pos = 4;
+    } else {
+        if (len < 6) return NGZ_E_INVALID;
+        pos = 6;
+        if (proto == 10) {  // field count (scope included), scope field count
+            n_fields = ngzh::rd16(tmpl + 2);
+            n_scope = ngzh::rd16(tmpl + 4);
+            if (n_scope > n_fields) return NGZ_E_INVALID;
+        } else {  // scope bytes, option bytes
+            scope_end = pos + ngzh::rd16(tmpl + 2);
+            end = scope_end + ngzh::rd16(tmpl + 4);
+            if (end > len) return NGZ_E_INVALID;
+        }
+    }
+    std::vector<PlanField> pf;
+    const bool by_bytes = options && proto == 9;
+    while (by_bytes ? pos < end : pf.size() < n_fields) {
+        if (pos + 4 > len) return NGZ_E_INVALID;
+        uint32_t code = ngzh::rd16(tmpl + pos);
+        const uint32_t L = ngzh::rd16(tmpl + pos + 2);
+        pos += 4;
+        const bool scope = by_bytes ? pos - 4 < scope_end : pf.size() < n_scope;
+        uint32_t pen = 0;
+        if (!(by_bytes && scope) && (code & 0x8000)) {  // NetFlow v9 scope codes are raw
+            if (pos + 4 > len) return NGZ_E_INVALID;
+            pen = ngzh::rd32(tmpl + pos);
+            pos += 4;
+            code &= 0x7FFF;
+        }
+        uint16_t pw = 0;
+        const int pi = pen == 0 ? param_index((uint16_t)code, &pw) : -1;
+        // the lengths field_rule decodes into the IE's full-width column (reduced-size encoding)
+        bool usable = false;
+        if (pi >= 0) usable = pw == 8 ? L == 8 : pw == 1 ? L == 1 : (L >= 1 && L <= pw);
+        else if (pen == 0 && is_count_ie((uint16_t)code)) usable = L >= 1 && L <= 8;
+        pf.push_back(PlanField{pen, (uint16_t)code, scope, usable});
+        if (pf.size() > 0x7FFF) return NGZ_E_INVALID;
+    }
+    build_plan(pf, out);
+    return NGZ_OK;
+}
+
+}  // extern "C"
