@@ -49,8 +49,8 @@
  *   - ngz_agg_push still explodes options records after an apply (the reference would have
  *     dropped them before aggregation);
  *   - an aggregation config that names isRenormalized sees None;
- *   - enrichment is not built (it would copy sampling IEs from options data into records): only
- *     sampling IEs carried in the record itself take effect, as logic.rs reads exactly those.
+ *   - ngz_renorm_apply reads only sampling IEs carried in the record itself; the ones an enrichment
+ *     resolved (flow_enrich.h) act through ngz_renorm_apply_enriched.
  *
  * Return codes as flow_decode.h (0 = ok, NGZ_E_*).  A renormalizer is not thread-safe.
  */
@@ -93,6 +93,18 @@ const char *ngz_renorm_last_error(ngz_renorm *r);
  * batch, before a context created at a destroyed one's address is applied. */
 int ngz_renorm_apply(ngz_renorm *r, ngz_ctx *ctx, const ngz_batch_out *out, ngz_renorm_stats *batch_stats /* may be NULL */,
                      void *hip_stream);
+/* ngz_renorm_apply over enriched records: `e` must have applied this batch of ctx last
+ * (ngz_enrich_apply; NGZ_E_INVALID otherwise).  For each sampling parameter a row's value is the
+ * enrichment's added column of that IE where the row's presence bit is set (of several occurrence
+ * indexes the highest present: appended fields come last and logic.rs:327-341 keeps the last),
+ * otherwise the record's own last occurrence.  An added column takes part when it is in the IE's
+ * canonical encoding (NGZ_K_UINT of the IE's width).  A slot with no sampling IE in its template
+ * but one among its added columns launches.  Counts, flags, the five counters, the refusals and
+ * the cached-view invalidation are ngz_renorm_apply's.  NGZ_E_LIMIT also for more than 16 added
+ * sampling columns in one slot.  An addition to ABI version 1: no existing signature changed. */
+struct ngz_enrich;
+int ngz_renorm_apply_enriched(ngz_renorm *r, struct ngz_enrich *e, ngz_ctx *ctx, const ngz_batch_out *out,
+                              ngz_renorm_stats *batch_stats /* may be NULL */, void *hip_stream);
 int ngz_renorm_totals(ngz_renorm *r, ngz_renorm_stats *totals, int reset);
 
 /* Per row of a slot of the batch last applied: bit 0 = isRenormalized(true) was appended.

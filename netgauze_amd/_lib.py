@@ -68,9 +68,23 @@ AGG_FUNCTIONS = [
 RENORM_FUNCTIONS = [
     "ngz_renorm_abi_version", "ngz_renorm_create", "ngz_renorm_destroy", "ngz_renorm_last_error", "ngz_renorm_apply",
     "ngz_renorm_totals", "ngz_renorm_flags", "ngz_renorm_batch_json", "ngz_renorm_last_timing",
-    "ngz_renorm_template_plan",
+    "ngz_renorm_template_plan", "ngz_renorm_apply_enriched",
 ]
 NGZ_RENORM_ABI_VERSION = 1
+# include/ngz/flow_enrich.h
+ENRICH_FUNCTIONS = [
+    "ngz_enrich_abi_version", "ngz_enrich_create", "ngz_enrich_destroy", "ngz_enrich_last_error", "ngz_enrich_writer_id",
+    "ngz_enrich_set_option", "ngz_enrich_op", "ngz_enrich_peer_count", "ngz_enrich_generation", "ngz_enrich_lookup",
+    "ngz_enrich_apply", "ngz_enrich_totals", "ngz_enrich_slot_columns", "ngz_enrich_row_fields", "ngz_enrich_value_arena", "ngz_enrich_forget", "ngz_enrich_batch_json",
+    "ngz_enrich_template_plan",
+    "ngz_enrich_last_timing",
+]
+NGZ_ENRICH_ABI_VERSION = 1
+NGZ_ENRICH_UPSERT, NGZ_ENRICH_DELETE, NGZ_ENRICH_DELETE_ALL = 1, 2, 3
+NGZ_ENRICH_OPT_TABLE_BITS = 1
+NGZ_ENRICH_OPTIONS = 0x100
+NGZ_ENRICH_MAX_SCOPE_FIELDS, NGZ_ENRICH_MAX_SHAPES, NGZ_ENRICH_MAX_COLUMNS = 4, 8, 32
+NGZ_ENRICH_MAX_KEY_BYTES, NGZ_ENRICH_MAX_DOMAINS = 16, 253
 NGZ_RENORM_OPTIONS = 0x100
 NGZ_E_INVALID, NGZ_E_DEVICE, NGZ_E_NOMEM, NGZ_E_LIMIT = -1, -2, -3, -4
 NGZ_AGG_KEY, NGZ_AGG_ADD, NGZ_AGG_MIN, NGZ_AGG_MAX, NGZ_AGG_OR = range(5)
@@ -208,6 +222,80 @@ class RenormPlan(ctypes.Structure):
 
 
 assert ctypes.sizeof(RenormStats) == 40 and ctypes.sizeof(RenormPlan) == 152
+
+class EnrichPeer(ctypes.Structure):
+    """ngz_enrich_peer: an exporter's IpAddr."""
+    _fields_ = [("family", ctypes.c_uint8), ("reserved", ctypes.c_uint8 * 3), ("addr", ctypes.c_uint8 * 16)]
+
+    @classmethod
+    def of(cls, ip):
+        import ipaddress
+        a = ipaddress.ip_address(ip)
+        p = cls()
+        p.family = a.version
+        for i, x in enumerate(a.packed):
+            p.addr[i] = x
+        return p
+
+
+class EnrichField(ctypes.Structure):
+    """ngz_enrich_field: an IE and its value in the canonical column encoding."""
+    _fields_ = [("pen", ctypes.c_uint32), ("ie_id", ctypes.c_uint16), ("kind", ctypes.c_uint8),
+                ("reserved", ctypes.c_uint8), ("len", ctypes.c_uint32), ("reserved2", ctypes.c_uint32),
+                ("value", ctypes.c_void_p)]
+
+
+class EnrichIe(ctypes.Structure):
+    _fields_ = [("pen", ctypes.c_uint32), ("ie_id", ctypes.c_uint16), ("reserved", ctypes.c_uint16)]
+
+
+class EnrichOperation(ctypes.Structure):
+    """ngz_enrich_operation: one EnrichmentOperation."""
+    _fields_ = [("kind", ctypes.c_uint8), ("weight", ctypes.c_uint8), ("reserved", ctypes.c_uint8 * 2),
+                ("peer", EnrichPeer), ("obs_domain_id", ctypes.c_uint32), ("n_scope", ctypes.c_uint32),
+                ("n_fields", ctypes.c_uint32), ("n_ies", ctypes.c_uint32), ("scope", ctypes.POINTER(EnrichField)),
+                ("fields", ctypes.POINTER(EnrichField)), ("ies", ctypes.POINTER(EnrichIe))]
+
+
+class EnrichResolved(ctypes.Structure):
+    """ngz_enrich_resolved: one resolved field of ngz_enrich_lookup."""
+    _fields_ = [("pen", ctypes.c_uint32), ("ie_id", ctypes.c_uint16), ("index", ctypes.c_uint16),
+                ("kind", ctypes.c_uint8), ("weight", ctypes.c_uint8), ("reserved", ctypes.c_uint16),
+                ("len", ctypes.c_uint32), ("value", ctypes.c_void_p)]
+
+
+class EnrichStats(ctypes.Structure):
+    """ngz_enrich_stats."""
+    _fields_ = [("records_processed", ctypes.c_uint64), ("records_matched", ctypes.c_uint64),
+                ("fields_added", ctypes.c_uint64), ("records_dropped", ctypes.c_uint64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class EnrichColumn(ctypes.Structure):
+    """ngz_enrich_column: one added column of a slot."""
+    _fields_ = [("pen", ctypes.c_uint32), ("ie_id", ctypes.c_uint16), ("index", ctypes.c_uint16),
+                ("kind", ctypes.c_uint8), ("is_string", ctypes.c_uint8), ("width", ctypes.c_uint16),
+                ("value_kind", ctypes.c_uint8), ("reserved", ctypes.c_uint8 * 3), ("data", ctypes.c_void_p)]
+
+
+class EnrichRef(ctypes.Structure):
+    _fields_ = [("pen", ctypes.c_uint32), ("ie_id", ctypes.c_uint16), ("index", ctypes.c_uint16)]
+
+
+class EnrichPlan(ctypes.Structure):
+    """ngz_enrich_plan (ngz_enrich_template_plan)."""
+    _fields_ = [("dropped", ctypes.c_uint8), ("launches", ctypes.c_uint8), ("n_shapes", ctypes.c_uint8),
+                ("n_columns", ctypes.c_uint8), ("shape_len", ctypes.c_uint8 * 8), ("shape", (EnrichRef * 4) * 8),
+                ("column", EnrichRef * 32), ("column_kind", ctypes.c_uint8 * 32), ("column_width", ctypes.c_uint16 * 32)]
+
+
+assert ctypes.sizeof(EnrichPlan) == 620
+
+
+assert (ctypes.sizeof(EnrichPeer), ctypes.sizeof(EnrichField), ctypes.sizeof(EnrichIe), ctypes.sizeof(EnrichOperation),
+        ctypes.sizeof(EnrichResolved), ctypes.sizeof(EnrichStats), ctypes.sizeof(EnrichColumn)) == (20, 24, 8, 64, 24, 32, 24)
 
 AGG_ROW_DTYPE = np.dtype([("window_start", "<u4"), ("flow_type", "u1"), ("reserved0", "u1"), ("peer", "<u2"),
                           ("key_present", "<u4"), ("val_present", "<u4"), ("record_count", "<u8"),
@@ -358,6 +446,8 @@ def load():
     lib.ngz_renorm_last_error.restype = ctypes.c_char_p
     lib.ngz_renorm_apply.argtypes = [P, P, ctypes.POINTER(BatchOut), ctypes.POINTER(RenormStats), P]
     lib.ngz_renorm_apply.restype = I
+    lib.ngz_renorm_apply_enriched.argtypes = [P, P, P, ctypes.POINTER(BatchOut), ctypes.POINTER(RenormStats), P]
+    lib.ngz_renorm_apply_enriched.restype = I
     lib.ngz_renorm_totals.argtypes = [P, ctypes.POINTER(RenormStats), I]
     lib.ngz_renorm_totals.restype = I
     lib.ngz_renorm_flags.argtypes = [P, U32, ctypes.POINTER(P), ctypes.POINTER(U32)]
@@ -368,6 +458,50 @@ def load():
     lib.ngz_renorm_last_timing.restype = I
     lib.ngz_renorm_template_plan.argtypes = [P, ctypes.c_size_t, I, ctypes.POINTER(RenormPlan)]
     lib.ngz_renorm_template_plan.restype = I
+    # enrichment (flow_enrich.h)
+    lib.ngz_enrich_abi_version.argtypes, lib.ngz_enrich_abi_version.restype = [], I
+    if lib.ngz_enrich_abi_version() != NGZ_ENRICH_ABI_VERSION:
+        raise RuntimeError("netgauze_amd: %s has enrichment ABI version %d, this binding needs %d -- rebuild it"
+                           % (LIB_PATH, lib.ngz_enrich_abi_version(), NGZ_ENRICH_ABI_VERSION))
+    lib.ngz_enrich_create.argtypes = [I, ctypes.c_char_p, ctypes.POINTER(P)]
+    lib.ngz_enrich_create.restype = I
+    lib.ngz_enrich_destroy.argtypes = [P]
+    lib.ngz_enrich_destroy.restype = None
+    lib.ngz_enrich_last_error.argtypes = [P]
+    lib.ngz_enrich_last_error.restype = ctypes.c_char_p
+    lib.ngz_enrich_writer_id.argtypes = [P]
+    lib.ngz_enrich_writer_id.restype = ctypes.c_char_p
+    lib.ngz_enrich_set_option.argtypes = [P, I, ctypes.c_int64]
+    lib.ngz_enrich_set_option.restype = I
+    lib.ngz_enrich_op.argtypes = [P, ctypes.POINTER(EnrichOperation)]
+    lib.ngz_enrich_op.restype = I
+    lib.ngz_enrich_peer_count.argtypes = [P]
+    lib.ngz_enrich_peer_count.restype = U64
+    lib.ngz_enrich_generation.argtypes = [P]
+    lib.ngz_enrich_generation.restype = U64
+    lib.ngz_enrich_lookup.argtypes = [P, ctypes.POINTER(EnrichPeer), U32, ctypes.POINTER(EnrichField), U32,
+                                      ctypes.POINTER(EnrichResolved), U32]
+    lib.ngz_enrich_lookup.restype = I
+    lib.ngz_enrich_apply.argtypes = [P, P, ctypes.POINTER(BatchOut), ctypes.POINTER(EnrichPeer),
+                                     ctypes.POINTER(EnrichStats), P]
+    lib.ngz_enrich_apply.restype = I
+    lib.ngz_enrich_totals.argtypes = [P, ctypes.POINTER(EnrichStats), I]
+    lib.ngz_enrich_totals.restype = I
+    lib.ngz_enrich_slot_columns.argtypes = [P, P, U32, ctypes.POINTER(EnrichColumn), U32, ctypes.POINTER(P),
+                                            ctypes.POINTER(U32)]
+    lib.ngz_enrich_row_fields.argtypes = [P, P, U32, U32, ctypes.POINTER(FieldValue), U32]
+    lib.ngz_enrich_row_fields.restype = I
+    lib.ngz_enrich_slot_columns.restype = I
+    lib.ngz_enrich_forget.argtypes = [P, P]
+    lib.ngz_enrich_forget.restype = I
+    lib.ngz_enrich_batch_json.argtypes = [P, P, P, P, JSON_LINE_FN, P]
+    lib.ngz_enrich_batch_json.restype = ctypes.c_int64
+    lib.ngz_enrich_template_plan.argtypes = [P, ctypes.POINTER(EnrichPeer), P, ctypes.c_size_t, I, ctypes.POINTER(EnrichPlan)]
+    lib.ngz_enrich_template_plan.restype = I
+    lib.ngz_enrich_value_arena.argtypes = [P, ctypes.POINTER(P), ctypes.POINTER(P), ctypes.POINTER(U64)]
+    lib.ngz_enrich_value_arena.restype = I
+    lib.ngz_enrich_last_timing.argtypes = [P, ctypes.POINTER(ctypes.c_float)]
+    lib.ngz_enrich_last_timing.restype = I
     # ingest (flow_ingest.h)
     lib.ngz_pcap_open.argtypes = [ctypes.c_char_p, ctypes.POINTER(P)]
     lib.ngz_pcap_open.restype = I

@@ -478,8 +478,22 @@ int json_render_mode(ngz_ctx *ctx, const JsonView &v, uint32_t d, std::string &o
                 put_field(o, ver_t.specs[f], fd, cols + (uint64_t)cap * fd.col_off + row * fd.width, v.bytes);
             }
             if (ver_t.n_scope == nf) o += "],\"fields\":[";
+            bool any = nf > ver_t.n_scope;
+            if (mode && !mode->enrich.empty()) {  // actor.rs:122-271: the resolved fields, then the writer id
+                const EnrichJsonSlot &es = mode->enrich[si.slot];
+                const uint32_t m = es.mask ? es.mask[row] : 0u;
+                for (size_t c = 0; c < es.cols.size(); ++c) {
+                    if (!((m >> c) & 1u)) continue;
+                    if (any) o += ',';
+                    any = true;
+                    json_put_added(o, es.cols[c], es.cols[c].data + row * es.cols[c].width, mode->arena);
+                }
+                if (any) o += ',';
+                any = true;
+                o += mode->writer_field;
+            }
             if (flags && (flags[row] & 1))  // logic.rs:371-374
-                o += nf > ver_t.n_scope ? ",{\"NetGauze\":{\"isRenormalized\":true}}" : "{\"NetGauze\":{\"isRenormalized\":true}}";
+                o += any ? ",{\"NetGauze\":{\"isRenormalized\":true}}" : "{\"NetGauze\":{\"isRenormalized\":true}}";
             o += "]}";
         }
         o += "]}}";
@@ -563,6 +577,18 @@ void put_cell(std::string &o, uint32_t pen, uint16_t id, uint8_t kind, uint16_t 
     fd.width = width;
     put_field(o, spec_of(pen, id), fd, cell, nullptr);
 }
+
+}  // namespace
+
+void ngzh::json_put_added(std::string &o, const EnrichJsonCol &c, const uint8_t *cell, const uint8_t *arena) {
+    DevField fd{};
+    fd.kind = c.kind;
+    fd.width = c.width;
+    fd.flags = c.kind == NGZ_K_VLEN && c.is_string ? 0x80 : 0;
+    put_field(o, spec_of(c.pen, c.ie), fd, cell, arena);
+}
+
+namespace {
 
 // a byte value of any length (BVAL keys / values): rendered as the decode path renders a
 // variable-length field of the IE (string text, or the bytes as a list)

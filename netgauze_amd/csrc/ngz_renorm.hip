@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "ngz/flow_renormalize.h"
+#include "ngz_enrich_internal.h"
 #include "ngz_host.h"
 #include "ngz_renorm_internal.h"
 #include "ngz_renorm_math.h"
@@ -19,6 +20,7 @@ namespace {
 
 constexpr uint32_t RN_THREADS = 256;
 constexpr uint32_t RN_ROWS_PER_LANE = 4;
+constexpr uint32_t RN_MAX_OV = 16;  // added sampling columns of an enrichment one slot may carry
 constexpr uint32_t RN_STATS = 3;  // device counters: renormalized, missing_or_invalid, inferred
 
 // What the kernel needs of one slot, passed by value
@@ -32,6 +34,14 @@ struct RnPlan {
     uint8_t *flags;              // one byte per row (room for a whole last quad)
     const uint32_t *bad;         // one bit per row: row of a message that did not decode
     unsigned long long *stats;   // [RN_STATS]
+    // ngz_renorm_apply_enriched: the enrichment's added columns of sampling IEs, in ascending
+    // FieldRef (appended fields come last, so a later one overrides: logic.rs:327-341)
+    uint32_t n_ov;
+    uint32_t reserved2;
+    const uint32_t *ov_mask;     // the enrichment's presence word per row
+    const uint8_t *ov_col[RN_MAX_OV];
+    uint8_t ov_param[RN_MAX_OV];
+    uint8_t ov_bit[RN_MAX_OV];
 };
 
 // IE -> parameter index, its column width (field_rule's for the IE's data type), or -1
@@ -107,6 +117,39 @@ __global__ __launch_bounds__(RN_THREADS) void k_renorm(const RnPlan P) {
             const double2 b = *(const double2 *)(P.param[NGZ_RN_P311] + 8ull * r0 + 16);
             prm[0].probability311 = a.x; prm[1].probability311 = a.y;
             prm[2].probability311 = b.x; prm[3].probability311 = b.y;
+        }
+        if (P.n_ov) {  // a row's value is the added column's where its presence bit is set
+            const uint4 mk = *(const uint4 *)(P.ov_mask + r0);  // the mask buffer is padded to a quad
+            const uint32_t mk4[4] = {mk.x, mk.y, mk.z, mk.w};
+            for (uint32_t o = 0; o < P.n_ov; ++o) {
+                const uint32_t pi = P.ov_param[o], bit = P.ov_bit[o];
+                uint32_t v[4] = {0, 0, 0, 0};
+                double dv[4] = {0, 0, 0, 0};
+                if (pi == NGZ_RN_P311) {
+                    const double2 a = *(const double2 *)(P.ov_col[o] + 8ull * r0);
+                    const double2 b = *(const double2 *)(P.ov_col[o] + 8ull * r0 + 16);
+                    dv[0] = a.x; dv[1] = a.y; dv[2] = b.x; dv[3] = b.y;
+                } else {
+                    rn_load4(P.ov_col[o], ((1u << pi) & RN_W1) ? 1u : ((1u << pi) & RN_W2) ? 2u : 4u, r0, v);
+                }
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    if (!((mk4[j] >> bit) & 1u)) continue;
+                    prm[j].present |= 1u << pi;
+                    switch (pi) {
+                    case NGZ_RN_P34: prm[j].interval34 = v[j]; break;
+                    case NGZ_RN_P35: prm[j].algorithm35 = v[j]; break;
+                    case NGZ_RN_P49: prm[j].mode49 = v[j]; break;
+                    case NGZ_RN_P50: prm[j].interval50 = v[j]; break;
+                    case NGZ_RN_P304: prm[j].selector304 = v[j]; break;
+                    case NGZ_RN_P305: prm[j].interval305 = v[j]; break;
+                    case NGZ_RN_P306: prm[j].space306 = v[j]; break;
+                    case NGZ_RN_P309: prm[j].size309 = v[j]; break;
+                    case NGZ_RN_P310: prm[j].population310 = v[j]; break;
+                    default: prm[j].probability311 = dv[j]; break;
+                    }
+                }
+            }
         }
         double k[RN_ROWS_PER_LANE];
         uint32_t scale = 0;  // rows with a factor
@@ -304,8 +347,11 @@ void ngz_renorm_destroy(ngz_renorm *r) {
 
 const char *ngz_renorm_last_error(ngz_renorm *r) { return r ? r->last_error.c_str() : "null renormalizer"; }
 
-int ngz_renorm_apply(ngz_renorm *r, ngz_ctx *ctx, const ngz_batch_out *out, ngz_renorm_stats *batch_stats,
-                     void *hip_stream) {
+}  // extern "C"
+
+// ngz_renorm_apply, and with `enriched` (an enricher's results for this batch) ngz_renorm_apply_enriched
+static int renorm_apply(ngz_renorm *r, const std::vector<ngze::SlotResult> *enriched, ngz_ctx *ctx, const ngz_batch_out *out,
+                        ngz_renorm_stats *batch_stats, void *hip_stream) {
     if (!r || !ctx || !out) return NGZ_E_INVALID;
     if (batch_stats) memset(batch_stats, 0, sizeof *batch_stats);
     if (ctx->device != r->device) return rfail(r, NGZ_E_INVALID, "the context is on another device");
@@ -354,6 +400,27 @@ int ngz_renorm_apply(ngz_renorm *r, ngz_ctx *ctx, const ngz_batch_out *out, ngz_
         }
         if (!build_plan(pf, &w.plan))
             return rfail(r, NGZ_E_LIMIT, "a template with more than 64 count fields");
+        // the enrichment's added columns of sampling IEs (canonical encoding: NGZ_K_UINT of the IE's width)
+        if (enriched && !w.plan.dropped && s < enriched->size() && (*enriched)[s].rows == si.n_records) {
+            const ngze::SlotResult &er = (*enriched)[s];
+            for (size_t c = 0; c < er.cols.size(); ++c) {
+                uint16_t pw = 0;
+                const int pi = er.cols[c].pen == 0 ? param_index(er.cols[c].ie_id, &pw) : -1;
+                if (pi < 0 || er.cols[c].kind != NGZ_K_UINT || er.cols[c].width != pw || !er.cols[c].data) continue;
+                if (w.k.n_ov == RN_MAX_OV) return rfail(r, NGZ_E_LIMIT, "more than 16 added sampling columns in one slot");
+                w.k.ov_col[w.k.n_ov] = er.cols[c].data;
+                w.k.ov_param[w.k.n_ov] = (uint8_t)pi;
+                w.k.ov_bit[w.k.n_ov] = (uint8_t)c;
+                ++w.k.n_ov;
+            }
+            if (w.k.n_ov) {
+                size_t n_count_fields = 0;
+                for (const PlanField &f : pf) n_count_fields += !f.scope && f.pen == 0 && f.usable && is_count_ie(f.ie);
+                if (n_count_fields > NGZ_RENORM_MAX_COUNTS) return rfail(r, NGZ_E_LIMIT, "a template with more than 64 count fields");
+                w.k.ov_mask = er.mask;
+                w.plan.launches = 1;
+            }
+        }
         if (!w.plan.launches) continue;
         if (!si.columns || ((uintptr_t)si.columns & 15) || (si.capacity & 3) || si.capacity < si.n_records)
             return rfail(r, NGZ_E_LIMIT, "unexpected column block alignment");
@@ -440,6 +507,23 @@ int ngz_renorm_apply(ngz_renorm *r, ngz_ctx *ctx, const ngz_batch_out *out, ngz_
     return NGZ_OK;
 }
 
+extern "C" {
+
+int ngz_renorm_apply(ngz_renorm *r, ngz_ctx *ctx, const ngz_batch_out *out, ngz_renorm_stats *batch_stats,
+                     void *hip_stream) {
+    return renorm_apply(r, nullptr, ctx, out, batch_stats, hip_stream);
+}
+
+int ngz_renorm_apply_enriched(ngz_renorm *r, ngz_enrich *e, ngz_ctx *ctx, const ngz_batch_out *out,
+                              ngz_renorm_stats *batch_stats, void *hip_stream) {
+    if (!r || !e || !ctx || !out) return NGZ_E_INVALID;
+    if (batch_stats) memset(batch_stats, 0, sizeof *batch_stats);
+    const std::vector<ngze::SlotResult> *res = ngze::results_for(e, ctx);
+    if (ngze::enrich_device(e) != r->device) return rfail(r, NGZ_E_INVALID, "the enricher is on another device");
+    if (!res) return rfail(r, NGZ_E_INVALID, "the enricher has not applied the context's last batch");
+    return renorm_apply(r, res, ctx, out, batch_stats, hip_stream);
+}
+
 int ngz_renorm_totals(ngz_renorm *r, ngz_renorm_stats *totals, int reset) {
     if (!r || !totals) return NGZ_E_INVALID;
     *totals = r->totals;
@@ -455,20 +539,30 @@ int ngz_renorm_flags(ngz_renorm *r, uint32_t slot, const uint8_t **dev_flags, ui
     return NGZ_OK;
 }
 
-int64_t ngz_renorm_batch_json(ngz_renorm *r, ngz_ctx *ctx, const uint8_t *host_bytes, ngz_json_line_fn fn, void *user) {
-    if (!r || !ctx || !fn) return NGZ_E_INVALID;
+}  // extern "C"
+
+int ngzh::renorm_flags_host(ngz_renorm *r, ngz_ctx *ctx, std::vector<uint8_t> &flags, std::vector<const uint8_t *> &slot_flags) {
     if (r->last_ctx != ctx || r->last_serial != ctx->batch_serial || ctx->async.pending.load())
         return rfail(r, NGZ_E_INVALID, "the context's last batch is not the batch last applied");
     RN_HIP(r, hipSetDevice(r->device));
     const size_t S = r->slot_rows.size();
     if (S != ctx->slot_infos.size()) return rfail(r, NGZ_E_INVALID, "slot table");
     const uint64_t total = S ? r->flag_off[S - 1] + (((uint64_t)r->slot_rows[S - 1] + 15) & ~15ull) : 0;
-    std::vector<uint8_t> flags(total + 1);
+    flags.assign(total + 1, 0);
     if (total) RN_HIP(r, hipMemcpy(flags.data(), r->d_flags.p, total, hipMemcpyDeviceToHost));
-    ngzh::RenormJson mode;
-    mode.slot_flags.assign(S, nullptr);
+    slot_flags.assign(S, nullptr);
     for (size_t s = 0; s < S; ++s)
-        if (r->slot_rows[s]) mode.slot_flags[s] = flags.data() + r->flag_off[s];
+        if (r->slot_rows[s]) slot_flags[s] = flags.data() + r->flag_off[s];
+    return NGZ_OK;
+}
+
+extern "C" {
+
+int64_t ngz_renorm_batch_json(ngz_renorm *r, ngz_ctx *ctx, const uint8_t *host_bytes, ngz_json_line_fn fn, void *user) {
+    if (!r || !ctx || !fn) return NGZ_E_INVALID;
+    std::vector<uint8_t> flags;
+    ngzh::RenormJson mode;
+    if (const int frc = ngzh::renorm_flags_host(r, ctx, flags, mode.slot_flags)) return frc;
     ngzh::JsonView v;
     const int rc = ngzh::json_view_load(ctx, host_bytes, v);
     if (rc) return rfail(r, rc, "json_view_load");

@@ -84,6 +84,15 @@ class FlowRenormalizer:
                                            ctypes.c_void_p(stream) if stream else None))
         return st.as_dict()
 
+    def apply_enriched(self, batch, enricher, stream=None):
+        """apply() over enriched records: the sampling IEs `enricher` (a FlowEnricher that applied this
+        batch last) resolved override the record's own (ngz_renorm_apply_enriched)."""
+        self._fresh(batch)
+        st = _lib.RenormStats()
+        self._check(lib().ngz_renorm_apply_enriched(self._h, enricher._h, batch._codec._ctx, ctypes.byref(batch.out),
+                                                    ctypes.byref(st), ctypes.c_void_p(stream) if stream else None))
+        return st.as_dict()
+
     def totals(self, reset=False):
         st = _lib.RenormStats()
         self._check(lib().ngz_renorm_totals(self._h, ctypes.byref(st), 1 if reset else 0))
