@@ -65,9 +65,9 @@
  * columns per slot plan, NGZ_ENRICH_MAX_DOMAINS observation domains per peer (ngz_enrich_apply).
  *
  * Out of scope:
- *   - the flow-options input (inputs/flow_options/normalize.rs: options data records turned into
- *     operations, with its interface and VRF normalization), the file and Kafka inputs, the serde
- *     JSON of EnrichmentOperation: operations come through ngz_enrich_op;
+ *   - the file and Kafka inputs, the serde JSON of EnrichmentOperation: operations come through
+ *     ngz_enrich_op (the flow-options input, inputs/flow_options/normalize.rs: options data records
+ *     turned into operations, is include/ngz/flow_options.h and feeds ngz_enrich_op);
  *   - the debug! logs;
  *   - aggregation keys or values over added columns: ngz_agg_push does not see them;
  *   - scope fields of float, string, octet, list or unknown kinds;

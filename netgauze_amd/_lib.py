@@ -83,6 +83,17 @@ NGZ_ENRICH_ABI_VERSION = 1
 NGZ_ENRICH_UPSERT, NGZ_ENRICH_DELETE, NGZ_ENRICH_DELETE_ALL = 1, 2, 3
 NGZ_ENRICH_OPT_TABLE_BITS = 1
 NGZ_ENRICH_OPTIONS = 0x100
+# include/ngz/flow_options.h
+OPTIONS_FUNCTIONS = [
+    "ngz_options_abi_version", "ngz_options_create", "ngz_options_destroy", "ngz_options_last_error",
+    "ngz_options_template_plan", "ngz_options_harvest", "ngz_options_op_count", "ngz_options_op", "ngz_options_feed",
+    "ngz_options_totals", "ngz_options_last_timing", "ngz_options_last_launches",
+]
+NGZ_OPTIONS_ABI_VERSION = 1
+NGZ_OPTIONS_OPTIONS = 0x100
+NGZ_OPTIONS_MAX_REFS = 24
+OPTIONS_CLASSES = {0: "none", 1: "sampling", 2: "interface", 3: "vrf", 4: "unclassified"}
+OPTIONS_OUTCOMES = {0: "ops", 1: "not_options", 2: "conversion_error", 3: "missing_required_fields"}
 NGZ_ENRICH_MAX_SCOPE_FIELDS, NGZ_ENRICH_MAX_SHAPES, NGZ_ENRICH_MAX_COLUMNS = 4, 8, 32
 NGZ_ENRICH_MAX_KEY_BYTES, NGZ_ENRICH_MAX_DOMAINS = 16, 253
 NGZ_RENORM_OPTIONS = 0x100
@@ -294,6 +305,27 @@ class EnrichPlan(ctypes.Structure):
 assert ctypes.sizeof(EnrichPlan) == 620
 
 
+class OptionsStats(ctypes.Structure):
+    """ngz_options_stats."""
+    _fields_ = [("received_flows", ctypes.c_uint64), ("processed_options_records", ctypes.c_uint64),
+                ("operations_generated", ctypes.c_uint64), ("normalization_errors", ctypes.c_uint64),
+                ("netflow_v9_conversion_errors", ctypes.c_uint64), ("ops_refused", ctypes.c_uint64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class OptionsPlan(ctypes.Structure):
+    """ngz_options_plan (ngz_options_template_plan)."""
+    _fields_ = [("klass", ctypes.c_uint8), ("outcome", ctypes.c_uint8), ("n_ops", ctypes.c_uint8),
+                ("id_equal", ctypes.c_uint8), ("id_src", ctypes.c_uint16 * 2), ("n_scope", ctypes.c_uint8 * 2),
+                ("n_fields", ctypes.c_uint8 * 2), ("scope", (EnrichRef * 24) * 2), ("fields", (EnrichRef * 24) * 2),
+                ("scope_src", (ctypes.c_uint16 * 24) * 2), ("fields_src", (ctypes.c_uint16 * 24) * 2)]
+
+
+assert ctypes.sizeof(OptionsPlan) == 972 and ctypes.sizeof(OptionsStats) == 48
+
+
 assert (ctypes.sizeof(EnrichPeer), ctypes.sizeof(EnrichField), ctypes.sizeof(EnrichIe), ctypes.sizeof(EnrichOperation),
         ctypes.sizeof(EnrichResolved), ctypes.sizeof(EnrichStats), ctypes.sizeof(EnrichColumn)) == (20, 24, 8, 64, 24, 32, 24)
 
@@ -502,6 +534,34 @@ def load():
     lib.ngz_enrich_value_arena.restype = I
     lib.ngz_enrich_last_timing.argtypes = [P, ctypes.POINTER(ctypes.c_float)]
     lib.ngz_enrich_last_timing.restype = I
+    # flow-options input (flow_options.h)
+    lib.ngz_options_abi_version.argtypes, lib.ngz_options_abi_version.restype = [], I
+    if lib.ngz_options_abi_version() != NGZ_OPTIONS_ABI_VERSION:
+        raise RuntimeError("netgauze_amd: %s has flow-options ABI version %d, this binding needs %d -- rebuild it"
+                           % (LIB_PATH, lib.ngz_options_abi_version(), NGZ_OPTIONS_ABI_VERSION))
+    lib.ngz_options_create.argtypes = [I, ctypes.c_uint8, ctypes.POINTER(P)]
+    lib.ngz_options_create.restype = I
+    lib.ngz_options_destroy.argtypes = [P]
+    lib.ngz_options_destroy.restype = None
+    lib.ngz_options_last_error.argtypes = [P]
+    lib.ngz_options_last_error.restype = ctypes.c_char_p
+    lib.ngz_options_template_plan.argtypes = [P, ctypes.c_size_t, I, ctypes.POINTER(OptionsPlan)]
+    lib.ngz_options_template_plan.restype = I
+    lib.ngz_options_harvest.argtypes = [P, P, ctypes.POINTER(BatchOut), ctypes.POINTER(EnrichPeer),
+                                        ctypes.POINTER(OptionsStats), P]
+    lib.ngz_options_harvest.restype = I
+    lib.ngz_options_op_count.argtypes = [P]
+    lib.ngz_options_op_count.restype = U64
+    lib.ngz_options_op.argtypes = [P, U64, ctypes.POINTER(EnrichOperation)]
+    lib.ngz_options_op.restype = I
+    lib.ngz_options_feed.argtypes = [P, P, ctypes.POINTER(U64)]
+    lib.ngz_options_feed.restype = I
+    lib.ngz_options_totals.argtypes = [P, ctypes.POINTER(OptionsStats), I]
+    lib.ngz_options_totals.restype = I
+    lib.ngz_options_last_timing.argtypes = [P, ctypes.POINTER(ctypes.c_float)]
+    lib.ngz_options_last_timing.restype = I
+    lib.ngz_options_last_launches.argtypes = [P]
+    lib.ngz_options_last_launches.restype = I
     # ingest (flow_ingest.h)
     lib.ngz_pcap_open.argtypes = [ctypes.c_char_p, ctypes.POINTER(P)]
     lib.ngz_pcap_open.restype = I
