@@ -244,6 +244,104 @@ int64_t ngz_agg_row_bytes(ngz_agg *a, const void *row, int is_value, uint32_t in
 int64_t ngz_agg_flowinfo_json(ngz_agg *a, const void *rows, uint64_t n, uint32_t shard_id, uint32_t seq0,
                               int64_t export_time_ms, ngz_json_line_fn fn, void *user);
 
+/* ---- aggregation over enriched records: the link enrichment -> aggregation ----
+ *
+ * ngz_agg_push over the records as the enrichment actor leaves them (include/ngz/flow_enrich.h):
+ * `e` must have applied the batch last decoded on ctx (ngz_enrich_apply; the check behind
+ * ngz_enrich_slot_columns).  NGZ_E_INVALID when it has not, when its results are of an earlier
+ * decode, when the enricher or the context is on another device, or when a decode is pending on
+ * ctx.  ngz_renorm_apply_enriched may have run in between (the scaled counts are summed then); it
+ * need not.
+ *
+ * The record the aggregation sees (enrichment/actor.rs:141-153, :176-187): the record's own
+ * non-scope fields in template order, then the fields the cache resolved for it, in ascending
+ * (PEN, IE id, cache index) -- the order of ngz_enrich_slot_columns; only the columns whose mask
+ * bit is set for the row -- then NetGauze dataCollectionManifestName(writer_id) (PEN 3746, id 7).
+ * FieldRef lookup (types.rs:82-100, aggregator.rs:308-330): the index of a key / aggregated field
+ * (IE, i) is the occurrence of the IE over that whole list.  With c occurrences of the IE among
+ * the template's non-scope fields:
+ *   i <  c   the template's own column, present for every row (ngz_agg_push's behaviour);
+ *   i >= c   the (i - c)-th added column of the IE that is present IN THIS ROW: presence is per
+ *            row, a row whose mask lacks it has None for that field.  The cache's own index of an
+ *            added field does not matter, only its rank among the present ones (a lone cache field
+ *            (X, 1) is occurrence c + 0);
+ *   the IE is dataCollectionManifestName: one more occurrence after the row's added columns of
+ *            that IE, present on every enriched row, its value the enricher's writer id.
+ * Parity unpinned: when one row gets two or more added fields of the same IE, the reference's
+ * indices among them follow FxHashMap order (here ascending cache index).  Everything else above
+ * is independent of that order.
+ * Dropped records (actor.rs:178, :237): a slot whose template has scope fields contributes no item:
+ * its records join no group, count in no record_count, add no template id or domain to the sets
+ * and are never late; a datagram whose only records are dropped does not advance the peer's
+ * event time (it explodes to zero items, aggregation.rs:124-172).
+ * Everything else is ngz_agg_push: group identity, lateness, window closing, the reductions and
+ * their Ord rules, None + Some -> Some, float sums in record order, all-or-nothing.
+ * A selected field that lands on an added column follows the type rules of a template column
+ * (NGZ_E_LIMIT: a fixed-size key on a NGZ_K_VLEN column, a width differing from the IE's under
+ * packed keys, a value width differing between slots); byte-valued keys and values take
+ * NGZ_K_STR / NGZ_K_BYTES / NGZ_K_VLEN added columns (variable-length cells point into the
+ * enricher's value arena; the push copies what it keeps: nothing of the enricher must outlive the
+ * call).  Also NGZ_E_LIMIT: several added columns of one IE selected in one slot that differ in
+ * kind or width.
+ * A push in which any selected field resolves to an added column or the writer id takes the
+ * general reduction path (ngz_agg_last_path); one in which none does, in any slot, chooses its
+ * path exactly as ngz_agg_push does.  Added without raising NGZ_AGG_ABI_VERSION (no struct or
+ * signature changed): a host that may meet an older library looks the symbol up. */
+typedef struct ngz_enrich ngz_enrich;
+int ngz_agg_push_enriched(ngz_agg *a, ngz_enrich *e, ngz_ctx *ctx, const ngz_batch_out *out, const ngz_peer *peer,
+                          int64_t collection_time_ms, uint64_t *late_records, void *hip_stream);
+
+/* Introspection, no device: how one FieldRef (pen, ie_id, index) resolves in a slot whose
+ * template has `fields` (template order, scope fields marked) and whose enrichment adds `cols`
+ * (ascending (PEN, IE id, index), as ngz_enrich_slot_columns lists them). */
+#define NGZ_AGG_ENRICH_MAX_COLUMNS 32 /* added columns per slot (NGZ_ENRICH_MAX_COLUMNS) */
+#define NGZ_AGG_RES_NONE 0   /* no row of the slot has the field */
+#define NGZ_AGG_RES_OWN 1    /* the template's own column: fields[own_field] */
+#define NGZ_AGG_RES_ADDED 2  /* per row: the ordinal-th of `candidates` present in the row; with
+                                writer_after, the writer id when exactly `ordinal` of them are present */
+#define NGZ_AGG_RES_WRITER 3 /* the writer id, on every enriched row */
+typedef struct {
+    uint32_t pen;
+    uint16_t ie_id;
+    uint8_t is_scope;
+    uint8_t reserved;
+} ngz_agg_slot_field;
+typedef struct {
+    uint32_t pen;
+    uint16_t ie_id;
+    uint16_t index;
+} ngz_agg_ref;
+typedef struct {
+    uint8_t kind;          /* NGZ_AGG_RES_* */
+    uint8_t dropped;       /* the template has scope fields: the slot contributes no item (kind NONE) */
+    uint8_t n_candidates;  /* NGZ_AGG_RES_ADDED */
+    uint8_t ordinal;       /* ... the wanted rank among the candidates present in a row */
+    uint8_t writer_after;  /* ... the IE is dataCollectionManifestName */
+    uint8_t reserved[3];
+    uint32_t own_field;    /* NGZ_AGG_RES_OWN: index into fields */
+    uint8_t candidates[32]; /* NGZ_AGG_ENRICH_MAX_COLUMNS indices into cols, ascending */
+} ngz_agg_enrich_resolution;
+int ngz_agg_enrich_field_plan(const ngz_agg_slot_field *fields, uint32_t n_fields, const ngz_agg_ref *cols,
+                              uint32_t n_cols, uint32_t pen, uint16_t ie_id, uint16_t index,
+                              ngz_agg_enrich_resolution *out);
+
+/* The resolve pass of ngz_agg_push_enriched for ONE selected field, over a presence mask and added
+ * columns given on the host (a test and bring-up door: the enrichment cache cannot leave every mask
+ * FieldRef::map_fields is defined for -- a scope that holds (X, 1) holds (X, 0) at no lower weight --
+ * but the pass must be right for all of them).  mask: one word per row; cols: n_cols columns of
+ * n_rows cells of `width` bytes (1..16), column c at cols + c * n_rows * width, bit c of the mask;
+ * cand: the candidate columns' bits; ordinal / writer_after as ngz_agg_enrich_resolution (the
+ * writer id needs width 16: a variable-length cell {0, 0, writer_len, 1}).  Out: present[row] = 1
+ * when the field is Some, cells: the chosen cell per row (zero when None).  Synchronous, on the
+ * device's default stream; allocates and frees its own buffers. */
+int ngz_agg_resolve_rows(int device, const uint32_t *mask, uint32_t n_rows, const uint8_t *cols, uint32_t n_cols,
+                         uint32_t width, uint32_t cand, uint32_t ordinal, int writer_after, uint32_t writer_len,
+                         uint32_t *present, uint8_t *cells);
+
+/* Device time of the resolve launches of the last ngz_agg_push_enriched (HIP events around them;
+ * 0 when it launched none), milliseconds.  Part of ngz_agg_last_timing's figure. */
+int ngz_agg_last_resolve_timing(ngz_agg *a, float *resolve_ms);
+
 /* Aggregator options (ngz_agg_set_option).  They choose how a push reduces, never what it
  * computes: every choice gives the same groups (tests/test_gpu_agg.py runs them against each
  * other and the oracle).  The library reads no tuning from the environment. */

@@ -69,7 +69,6 @@
  *     ngz_enrich_op (the flow-options input, inputs/flow_options/normalize.rs: options data records
  *     turned into operations, is include/ngz/flow_options.h and feeds ngz_enrich_op);
  *   - the debug! logs;
- *   - aggregation keys or values over added columns: ngz_agg_push does not see them;
  *   - scope fields of float, string, octet, list or unknown kinds;
  *
  * The value arena interns every variable-length value an upload met and is released only by

@@ -63,7 +63,9 @@ AGG_FUNCTIONS = [
     "ngz_agg_groups", "ngz_agg_flush", "ngz_agg_closed", "ngz_agg_emit", "ngz_agg_reset", "ngz_agg_sets",
     "ngz_agg_key_info", "ngz_agg_value_info", "ngz_agg_flowinfo_json", "ngz_agg_last_timing", "ngz_agg_peer", "ngz_agg_last_path",
     "ngz_agg_abi_version", "ngz_agg_row_bytes", "ngz_agg_set_option",
+    "ngz_agg_push_enriched", "ngz_agg_enrich_field_plan", "ngz_agg_resolve_rows", "ngz_agg_last_resolve_timing",
 ]
+NGZ_AGG_RES_NONE, NGZ_AGG_RES_OWN, NGZ_AGG_RES_ADDED, NGZ_AGG_RES_WRITER = 0, 1, 2, 3
 # include/ngz/flow_renormalize.h
 RENORM_FUNCTIONS = [
     "ngz_renorm_abi_version", "ngz_renorm_create", "ngz_renorm_destroy", "ngz_renorm_last_error", "ngz_renorm_apply",
@@ -291,6 +293,23 @@ class EnrichColumn(ctypes.Structure):
                 ("value_kind", ctypes.c_uint8), ("reserved", ctypes.c_uint8 * 3), ("data", ctypes.c_void_p)]
 
 
+class AggSlotField(ctypes.Structure):
+    """ngz_agg_slot_field (ngz_agg_enrich_field_plan)."""
+    _fields_ = [("pen", ctypes.c_uint32), ("ie_id", ctypes.c_uint16), ("is_scope", ctypes.c_uint8),
+                ("reserved", ctypes.c_uint8)]
+
+
+class AggRef(ctypes.Structure):
+    _fields_ = [("pen", ctypes.c_uint32), ("ie_id", ctypes.c_uint16), ("index", ctypes.c_uint16)]
+
+
+class AggEnrichResolution(ctypes.Structure):
+    """ngz_agg_enrich_resolution."""
+    _fields_ = [("kind", ctypes.c_uint8), ("dropped", ctypes.c_uint8), ("n_candidates", ctypes.c_uint8),
+                ("ordinal", ctypes.c_uint8), ("writer_after", ctypes.c_uint8), ("reserved", ctypes.c_uint8 * 3),
+                ("own_field", ctypes.c_uint32), ("candidates", ctypes.c_uint8 * 32)]
+
+
 class EnrichRef(ctypes.Structure):
     _fields_ = [("pen", ctypes.c_uint32), ("ie_id", ctypes.c_uint16), ("index", ctypes.c_uint16)]
 
@@ -433,6 +452,16 @@ def load():
     lib.ngz_agg_push.argtypes = [P, P, ctypes.POINTER(BatchOut), ctypes.POINTER(Peer), ctypes.c_int64,
                                  ctypes.POINTER(ctypes.c_uint64), P]
     lib.ngz_agg_push.restype = I
+    lib.ngz_agg_push_enriched.argtypes = [P, P, P, ctypes.POINTER(BatchOut), ctypes.POINTER(Peer), ctypes.c_int64,
+                                          ctypes.POINTER(ctypes.c_uint64), P]
+    lib.ngz_agg_push_enriched.restype = I
+    lib.ngz_agg_enrich_field_plan.argtypes = [ctypes.POINTER(AggSlotField), U32, ctypes.POINTER(AggRef), U32, U32,
+                                              ctypes.c_uint16, ctypes.c_uint16, ctypes.POINTER(AggEnrichResolution)]
+    lib.ngz_agg_enrich_field_plan.restype = I
+    lib.ngz_agg_resolve_rows.argtypes = [I, P, U32, P, U32, U32, U32, U32, I, U32, P, P]
+    lib.ngz_agg_resolve_rows.restype = I
+    lib.ngz_agg_last_resolve_timing.argtypes = [P, ctypes.POINTER(ctypes.c_float)]
+    lib.ngz_agg_last_resolve_timing.restype = I
     lib.ngz_agg_layout.argtypes = [P, ctypes.POINTER(U32), ctypes.POINTER(U32), ctypes.POINTER(ctypes.c_uint16),
                                    ctypes.POINTER(U32), ctypes.POINTER(ctypes.c_uint16)]
     lib.ngz_agg_layout.restype = I

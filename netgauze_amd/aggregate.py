@@ -70,6 +70,36 @@ def unify(transform):
     return out
 
 
+def enrich_field_plan(fields, cols, ref):
+    """ngz_agg_enrich_field_plan (no device): how FieldRef `ref` = (pen, ie_id, index) resolves in a
+    slot whose template has `fields` [(pen, ie_id, is_scope)] and whose enrichment adds `cols`
+    [(pen, ie_id, index)]: dict(kind, dropped, own_field, candidates, ordinal, writer_after)."""
+    fa = (_lib.AggSlotField * max(len(fields), 1))(*[_lib.AggSlotField(p, i, int(bool(sc)), 0) for p, i, sc in fields])
+    ca = (_lib.AggRef * max(len(cols), 1))(*[_lib.AggRef(p, i, x) for p, i, x in cols])
+    res = _lib.AggEnrichResolution()
+    rc = lib().ngz_agg_enrich_field_plan(fa, len(fields), ca, len(cols), ref[0], ref[1], ref[2], ctypes.byref(res))
+    if rc != 0:
+        raise AggError("ngz_agg_enrich_field_plan failed (%d)" % rc)
+    return dict(kind=res.kind, dropped=bool(res.dropped), own_field=res.own_field,
+                candidates=list(res.candidates)[:res.n_candidates], ordinal=res.ordinal,
+                writer_after=bool(res.writer_after))
+
+
+def resolve_rows(mask, cols, width, cand, ordinal, writer_after=False, writer_len=0, device=0):
+    """ngz_agg_resolve_rows: the device resolve pass of one selected field over a host mask (uint32 per
+    row) and host columns [n_cols][n_rows][width] (uint8).  Returns (present [n_rows], cells [n_rows, width])."""
+    mask = np.ascontiguousarray(mask, dtype=np.uint32)
+    cols = np.ascontiguousarray(cols, dtype=np.uint8).reshape(-1, len(mask), width)
+    present = np.zeros(len(mask), dtype=np.uint32)
+    cells = np.zeros((len(mask), width), dtype=np.uint8)
+    rc = lib().ngz_agg_resolve_rows(device, mask.ctypes.data, len(mask), cols.ctypes.data if len(cols) else None, len(cols),
+                                    width, cand, ordinal, int(writer_after), writer_len, present.ctypes.data,
+                                    cells.ctypes.data)
+    if rc != 0:
+        raise AggError("ngz_agg_resolve_rows failed (%d)" % rc)
+    return present, cells
+
+
 def _datetime_ms(ms):
     secs = ms // 1000
     return (secs, (ms - secs * 1000) * 1_000_000)
@@ -135,6 +165,18 @@ class FlowAggregator:
                                        collection_ms, ctypes.byref(late), None))
         return late.value
 
+    def push_enriched(self, batch, enricher, peer_port=4739, collection_ms=0, peer_ip=DEFAULT_PEER):
+        """push() over the records as the enrichment leaves them (ngz_agg_push_enriched): keys and
+        aggregated fields may land on the columns `enricher` (a FlowEnricher that applied this batch)
+        added, or on its writer id; records with scope fields are no items.  Returns the late records."""
+        if batch.generation != batch._codec.generation:
+            raise AggError("stale DecodedBatch: its codec has decoded another batch since")
+        late = ctypes.c_uint64()
+        peer = _lib.Peer.of(peer_ip, peer_port)
+        self._check(lib().ngz_agg_push_enriched(self._h, enricher._h, batch._codec._ctx, ctypes.byref(batch.out),
+                                                ctypes.byref(peer), collection_ms, ctypes.byref(late), None))
+        return late.value
+
     def peers(self):
         """Peer IPs of the rows last returned by flush / emit (row field `peer`)."""
         out = []
@@ -152,6 +194,12 @@ class FlowAggregator:
     def push_ms(self):
         t = ctypes.c_float()
         lib().ngz_agg_last_timing(self._h, ctypes.byref(t))
+        return t.value
+
+    def resolve_ms(self):
+        """Device time of the resolve launches of the last push_enriched (0: it launched none)."""
+        t = ctypes.c_float()
+        lib().ngz_agg_last_resolve_timing(self._h, ctypes.byref(t))
         return t.value
 
     def n_groups(self):

@@ -33,7 +33,9 @@ def _digest(patterns):
     return h.hexdigest()[:16]
 
 
-_AGG = ("netgauze_amd/csrc/ngz_agg.hip", "netgauze_amd/csrc/ngz_host.h", "netgauze_amd/csrc/ngz_internal.h",
+_AGG = ("netgauze_amd/csrc/ngz_agg.hip", "netgauze_amd/csrc/ngz_agg_enrich.hip", "netgauze_amd/csrc/ngz_agg_enrich.h",
+        "netgauze_amd/csrc/ngz_agg_enrich_plan.h", "netgauze_amd/csrc/ngz_agg_enrich_plan.cpp",
+        "netgauze_amd/csrc/ngz_enrich_internal.h", "include/ngz/flow_enrich.h", "netgauze_amd/csrc/ngz_host.h", "netgauze_amd/csrc/ngz_internal.h",
         "include/ngz/flow_aggregate.h", "include/ngz/flow_decode.h", "netgauze_amd/csrc/ie_table.inc")
 
 

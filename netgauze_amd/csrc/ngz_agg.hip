@@ -51,6 +51,9 @@
 
 #include "ngz/flow_aggregate.h"
 #include "ngz/flow_decode.h"
+#include "ngz_agg_enrich.h"
+#include "ngz_agg_enrich_plan.h"
+#include "ngz_enrich_internal.h"
 #include "ngz_host.h"
 
 namespace {
@@ -63,6 +66,7 @@ constexpr uint32_t DOM_SLOTS = 128;
 constexpr uint32_t SET_BITS = 64;
 constexpr uint32_t NEWDOM_SLOTS = 256;  // distinct new observation domains one push may bring
 constexpr uint64_t TAG_EMPTY = 0, TAG_TOMB = 1;
+constexpr uint64_t TAG_BUSY = 2;  // hashed keys, exact re-probe: a slot claimed whose key is being written
 constexpr uint32_t NONE = 0xFFFFFFFFu;
 constexpr uint32_t OWN_BIT = 0x80000000u;  // rec_g: the record is its group's owner (slots < 2^31)
 
@@ -119,7 +123,31 @@ struct AggSlotPlan {            // per batch slot, built on the host every push
     uint32_t usable;                            // 0: slot not aggregated (no records / not device-decoded)
     const uint8_t *bytes;                       // the batch bytes (variable-length cells point into them)
     uint32_t key_vlen, val_vlen;                // bit k / v: a variable-length column ({u64 offset, u32 length})
+    // ngz_agg_push_enriched (the kernels' ENR instantiations read these; the plain push leaves them 0)
+    uint32_t dropped;                           // the template has scope fields: its records are no items
+    uint32_t key_ext, val_ext;                  // bit k / v: variable-length cells point into xbytes, not bytes
+    const uint32_t *kpres, *vpres;              // per row: bit k / v = the field is Some (null: as key_col / val_col say)
+    const uint8_t *xbytes;                      // the enricher's value arena
+    const uint8_t *wid;                         // the writer id (cells whose word 3 is ngza::CELL_WRITER)
 };
+
+// Enriched push: a row's key / value presence word (plain push: every column the plan has)
+template <bool ENR>
+__device__ __forceinline__ uint32_t row_kp(const AggSlotPlan &sp, uint64_t row) {
+    if (ENR) {
+        const uint32_t *p = sp.kpres;
+        if (p) return p[row];
+    }
+    return ~0u;
+}
+template <bool ENR>
+__device__ __forceinline__ uint32_t row_vp(const AggSlotPlan &sp, uint64_t row) {
+    if (ENR) {
+        const uint32_t *p = sp.vpres;
+        if (p) return p[row];
+    }
+    return ~0u;
+}
 
 struct AggParams {
     uint32_t n_keys, n_vals;
@@ -217,11 +245,23 @@ __device__ __forceinline__ Span cell_span(const uint8_t *col, uint32_t w, bool v
     return Span{q, n};
 }
 
+// Enriched push: a variable-length cell of an added or resolved column points into the enricher's
+// value arena, or (word 3 set) at the writer id
+__device__ __forceinline__ Span ext_span(const AggSlotPlan &sp, const uint8_t *col, uint64_t row) {
+    const uint8_t *c = col + row * 16;
+    const uint8_t *base = *(const uint32_t *)(c + 12) ? sp.wid : sp.xbytes;
+    return Span{base + *(const uint64_t *)c, *(const uint32_t *)(c + 8)};
+}
+
+template <bool ENR>
 __device__ __forceinline__ Span key_span(const AggSlotPlan &sp, const AggParams &P, uint32_t k, uint64_t row) {
+    if (ENR && ((sp.key_ext >> k) & 1)) return ext_span(sp, sp.key_col[k], row);
     return cell_span(sp.key_col[k], sp.key_w[k], (sp.key_vlen >> k) & 1, (P.key_str >> k) & 1, sp.bytes, row);
 }
 
+template <bool ENR>
 __device__ __forceinline__ Span val_span(const AggSlotPlan &sp, uint32_t v, uint64_t row) {
+    if (ENR && ((sp.val_ext >> v) & 1)) return ext_span(sp, sp.val_col[v], row);
     return cell_span(sp.val_col[v], sp.val_w[v], (sp.val_vlen >> v) & 1, false, sp.bytes, row);
 }
 
@@ -285,7 +325,9 @@ struct KeyVal {
     uint32_t w[8];
 };
 
-__device__ __forceinline__ void key_words(const AggSlotPlan &sp, const AggParams &P, uint64_t row, KeyVal &kv) {
+template <bool ENR>
+__device__ __forceinline__ void key_words(const AggSlotPlan &sp, const AggParams &P, uint64_t row, uint32_t rkp,
+                                          KeyVal &kv) {
     bool nul = false;
 #pragma unroll
     for (uint32_t j = 0; j < 8; ++j) {
@@ -293,7 +335,7 @@ __device__ __forceinline__ void key_words(const AggSlotPlan &sp, const AggParams
         if (j >= P.kw_n) continue;
         const uint32_t k = P.kw_key[j], i = P.kw_idx[j];
         const uint8_t *c = sp.key_col[k];
-        if (!c) continue;
+        if (!c || (ENR && !((rkp >> k) & 1))) continue;
         const uint32_t w = sp.key_w[k];
         if (i == 0) nul = false;
         kv.w[j] = cell_word(c + row * w, w, i, false, nul);  // KeyVal keys are fixed cells
@@ -305,13 +347,16 @@ __device__ __forceinline__ uint32_t hdr_word(const AggSlotPlan &sp, const AggPar
     return sp.proto | (P.peer << 16);
 }
 
+template <bool ENR>
 __device__ __forceinline__ uint64_t key_tag(const AggSlotPlan &sp, const AggParams &P, uint64_t row, uint32_t win,
                                             uint32_t &present, KeyVal &kv) {
     present = 0;
+    const uint32_t rkp = row_kp<ENR>(sp, row);  // enriched push: the row's presence word
     if (P.packed) {  // exact tag: bit 63 | window/60 | flow type | peer | per key: presence bit + value bits
         uint64_t x = ((((uint64_t)(win / 60) << 1) | (sp.proto == 9)) << P.peer_bits) | P.peer;
         for (uint32_t k = 0; k < P.n_keys; ++k) {
             const uint8_t *c = sp.key_col[k];
+            if (ENR && !((rkp >> k) & 1)) c = nullptr;
             const uint32_t w = sp.key_w[k];
             uint64_t v = 0;
             if (c) {
@@ -325,12 +370,12 @@ __device__ __forceinline__ uint64_t key_tag(const AggSlotPlan &sp, const AggPara
     }
     uint64_t h = mix64(0x4E475A41474731ull, ((uint64_t)win << 32) | hdr_word(sp, P));
     if (P.kw_n) {
-        key_words(sp, P, row, kv);
+        key_words<ENR>(sp, P, row, rkp, kv);
 #pragma unroll
         for (uint32_t j = 0; j < 8; ++j) {
             if (j >= P.kw_n) continue;
             const uint32_t k = P.kw_key[j];
-            const bool has = sp.key_col[k] != nullptr;
+            const bool has = sp.key_col[k] != nullptr && (!ENR || ((rkp >> k) & 1));
             if (P.kw_idx[j] == 0) {
                 h = mix64(h, has ? 0x100u : 0u);
                 if (has) present |= 1u << k;
@@ -340,11 +385,12 @@ __device__ __forceinline__ uint64_t key_tag(const AggSlotPlan &sp, const AggPara
     } else {
         for (uint32_t k = 0; k < P.n_keys; ++k) {
             const uint8_t *c = sp.key_col[k];
+            if (ENR && !((rkp >> k) & 1)) c = nullptr;
             h = mix64(h, c ? 0x100u : 0u);
             if (!c) continue;
             present |= 1u << k;
             if (P.key_kind[k] == KK_BYTES) {  // its length and every byte
-                const Span s = key_span(sp, P, k, row);
+                const Span s = key_span<ENR>(sp, P, k, row);
                 h = mix64(h, s.n);
                 for (uint32_t j = 0; j < (s.n + 3) / 4; ++j) h = mix64(h, span_word(s.p, s.n, j));
                 continue;
@@ -354,7 +400,7 @@ __device__ __forceinline__ uint64_t key_tag(const AggSlotPlan &sp, const AggPara
         }
     }
     h &= P.hash_mask;
-    return h < 2 ? h + 2 : h;  // 0 / 1 are the empty and tombstone tags
+    return h < 3 ? h + 3 : h;  // 0 / 1 / 2 are the empty, tombstone and busy tags
 }
 
 // A slot's header and first 8 key words (KeyVal keys), loaded with three 16-byte loads
@@ -382,6 +428,7 @@ __device__ __forceinline__ bool key_row_equal(const KeyRow &kr, const AggSlotPla
     return same;
 }
 
+template <bool ENR>
 __device__ __forceinline__ bool key_equal(const uint8_t *R, const AggSlotPlan &sp, const AggParams &P, uint64_t row,
                                           uint32_t win, uint32_t kp, const KeyVal &kv) {
     if (P.kw_n) return key_row_equal(key_row_load(R, P), sp, P, win, kp, kv);
@@ -389,10 +436,10 @@ __device__ __forceinline__ bool key_equal(const uint8_t *R, const AggSlotPlan &s
                 *(const uint32_t *)(R + 8) == kp;
     for (uint32_t k = 0; k < P.n_keys && same; ++k) {
         const uint8_t *c = sp.key_col[k];
-        if (!c) continue;
+        if (!c || (ENR && !((kp >> k) & 1))) continue;  // kp: the record's present keys (key_tag)
         const uint32_t *rk = (const uint32_t *)(R + P.key_off[k]);
         if (P.key_kind[k] == KK_BYTES) {
-            const Span s = key_span(sp, P, k, row);
+            const Span s = key_span<ENR>(sp, P, k, row);
             same = rk[0] == s.n;
             for (uint32_t j = 0; j < BVAL_INLINE / 4 && same; ++j)
                 same = rk[2 + j] == span_word(s.p, min(s.n, BVAL_INLINE), j);
@@ -408,6 +455,7 @@ __device__ __forceinline__ bool key_equal(const uint8_t *R, const AggSlotPlan &s
     return same;
 }
 
+template <bool ENR>
 __device__ __forceinline__ void key_write(uint8_t *R, const AggSlotPlan &sp, const AggParams &P, uint64_t row,
                                           uint32_t win, uint32_t kp, const KeyVal &kv, unsigned int *__restrict__ err) {
     *(uint32_t *)(R + 0) = win;
@@ -422,12 +470,12 @@ __device__ __forceinline__ void key_write(uint8_t *R, const AggSlotPlan &sp, con
     for (uint32_t k = 0; k < P.n_keys; ++k) {
         uint32_t *dst = (uint32_t *)(R + P.key_off[k]);
         const uint8_t *c = sp.key_col[k];
-        if (!c) {
+        if (!c || (ENR && !((kp >> k) & 1))) {
             for (uint32_t j = 0; j < P.key_slot[k] / 4; ++j) dst[j] = 0;
             continue;
         }
         if (P.key_kind[k] == KK_BYTES) {
-            bval_write((uint8_t *)dst, key_span(sp, P, k, row), P, err);
+            bval_write((uint8_t *)dst, key_span<ENR>(sp, P, k, row), P, err);
             continue;
         }
         KeyWords kw{c + row * sp.key_w[k], sp.key_w[k]};
@@ -509,6 +557,15 @@ __global__ void k_agg_dgram(const ngz_set_info *__restrict__ sets, uint32_t n_se
                             uint32_t *__restrict__ has_rec) {
     for (uint32_t s = blockIdx.x * blockDim.x + threadIdx.x; s < n_sets; s += gridDim.x * blockDim.x)
         if (sets[s].n && sets[s].dgram < n_dgrams) has_rec[sets[s].dgram] = 1;
+}
+
+// ngz_agg_push_enriched: a datagram carries records when a set of a slot that is not dropped does
+// (records with scope fields explode to no item, aggregation.rs:124-172)
+__global__ void k_agg_dgram_kept(const ngz_set_info *__restrict__ sets, uint32_t n_sets, uint32_t n_dgrams,
+                                 const AggSlotPlan *__restrict__ plans, uint32_t n_slots, uint32_t *__restrict__ has_rec) {
+    for (uint32_t s = blockIdx.x * blockDim.x + threadIdx.x; s < n_sets; s += gridDim.x * blockDim.x)
+        if (sets[s].n && sets[s].dgram < n_dgrams && sets[s].slot < n_slots && !plans[sets[s].slot].dropped)
+            has_rec[sets[s].dgram] = 1;
 }
 
 __global__ void k_agg_ts(const ngz_dgram_hdr *__restrict__ hdr, const uint32_t *__restrict__ has_rec, uint32_t n,
@@ -604,6 +661,7 @@ __global__ void k_agg_recinfo(const ngz_set_info *__restrict__ sets, uint32_t n_
             ts = h.time;
             sysup = h.version == 9 ? h.sys_up_time : 0u;
             uint16_t info = dginfo[si.dgram];
+            if (plans[si.slot].dropped) info = 0;  // enriched push: no item, never late (actor.rs:178)
             if ((info & DG_USE) && plans[si.slot].usable) info |= DG_VALID;
             w = si.slot | ((uint32_t)info << 16);
         }
@@ -725,7 +783,7 @@ __device__ __forceinline__ void wave_append(uint32_t *__restrict__ list, CT *__r
 // per-push marker is set), or exact = true (records whose hash collided, re-probed after the
 // pass that wrote every key).  A slot claimed by another record of this same pass is taken
 // tentatively (*tentative): k_agg_check compares the keys once the pass is over.
-template <bool EXACT>
+template <bool EXACT, bool ENR>
 __device__ __forceinline__ uint32_t probe(const AggSlotPlan &sp, const AggParams &P, uint64_t row, uint32_t win,
                                           uint32_t kp, const KeyVal &kv, uint64_t h,
                                           unsigned long long *__restrict__ tags, uint8_t *__restrict__ rows,
@@ -734,12 +792,39 @@ __device__ __forceinline__ uint32_t probe(const AggSlotPlan &sp, const AggParams
     *tentative = *claimed = false;
     for (uint64_t probes = 0; probes <= P.mask; ++probes, g = (g + 1) & P.mask) {
         unsigned long long cur = tags[g];
+        bool won = false;
         if (cur == TAG_EMPTY) {
-            cur = atomicCAS(&tags[g], TAG_EMPTY, (unsigned long long)h);
+            // the exact re-probe compares keys at once, so its claims show their tag only when the key
+            // is written: another record of the same key that came by in between would find the tag,
+            // not the key, and claim a second slot for it
+            cur = atomicCAS(&tags[g], TAG_EMPTY, EXACT ? (unsigned long long)TAG_BUSY : (unsigned long long)h);
             if (cur == TAG_EMPTY) {
-                key_write(rows + g * P.row_bytes, sp, P, row, win, kp, kv, err);
+                key_write<ENR>(rows + g * P.row_bytes, sp, P, row, win, kp, kv, err);
+                if (!EXACT) {
+                    *claimed = true;
+                    return (uint32_t)g;
+                }
+                __threadfence();
+                atomicExch(&tags[g], (unsigned long long)h);
+                won = true;
+            }
+        }
+        if (EXACT) {
+            // A slot being claimed: its claimer only writes its key before it shows the tag, so a short
+            // bounded wait sees it.  The wave's own claimers are through by now (they leave below, after
+            // this wait); a record that still finds the slot busy joins the next round.
+            if (!won && cur == TAG_BUSY)
+                for (int spin = 0; spin < 1024 && cur == TAG_BUSY; ++spin) {
+                    __builtin_amdgcn_s_sleep(2);
+                    cur = __hip_atomic_load(&tags[g], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
+                }
+            if (won) {
                 *claimed = true;
                 return (uint32_t)g;
+            }
+            if (cur == TAG_BUSY) {
+                *tentative = true;
+                return NONE;
             }
         }
         if (cur != h) continue;
@@ -747,7 +832,7 @@ __device__ __forceinline__ uint32_t probe(const AggSlotPlan &sp, const AggParams
         const uint8_t *R = rows + g * P.row_bytes;
         // the marker is written by k_agg_apply* only: stable during this pass (loaded with the key)
         const uint32_t mark = EXACT ? 1u : *(const uint32_t *)(R + 36);
-        const bool eq = key_equal(R, sp, P, row, win, kp, kv);
+        const bool eq = key_equal<ENR>(R, sp, P, row, win, kp, kv);
         if (mark != 0) {
             if (eq) return (uint32_t)g;
             continue;
@@ -760,6 +845,7 @@ __device__ __forceinline__ uint32_t probe(const AggSlotPlan &sp, const AggParams
 }
 
 // First pass: every record of the push
+template <bool ENR>
 __global__ __launch_bounds__(256) void k_agg_claim(const RecCtx C, const AggParams P,
                                                    unsigned long long *__restrict__ tags, uint8_t *__restrict__ rows,
                                                    uint32_t *__restrict__ rec_g, uint32_t *__restrict__ claims,
@@ -781,8 +867,8 @@ __global__ __launch_bounds__(256) void k_agg_claim(const RecCtx C, const AggPara
                 const uint32_t ts = r.ts, win = ts - ts % 60;  // get_window_start
                 uint32_t kp;
                 KeyVal kv;
-                const uint64_t h = key_tag(sp, P, r.row, win, kp, kv);
-                g = probe<false>(sp, P, r.row, win, kp, kv, h, tags, rows, err, &tentative, &claimed);
+                const uint64_t h = key_tag<ENR>(sp, P, r.row, win, kp, kv);
+                g = probe<false, ENR>(sp, P, r.row, win, kp, kv, h, tags, rows, err, &tentative, &claimed);
             };
             if (su != NONE) go(C.plans[su]);
             else go(C.plans[r.slot]);
@@ -798,6 +884,7 @@ __global__ __launch_bounds__(256) void k_agg_claim(const RecCtx C, const AggPara
 // Hashed keys: compare each record's key with its slot's (all slots' keys are written by now);
 // a record on another key's slot (64-bit tag collision) is listed for the exact re-probe.
 // list == null: every record; else the records listed.
+template <bool ENR>
 __global__ __launch_bounds__(256) void k_agg_check(const RecCtx C, const AggParams P, const uint8_t *__restrict__ rows,
                                                    uint32_t *__restrict__ rec_g, const uint32_t *__restrict__ list,
                                                    uint32_t n_list, uint32_t *__restrict__ collided,
@@ -814,8 +901,8 @@ __global__ __launch_bounds__(256) void k_agg_check(const RecCtx C, const AggPara
         const uint32_t ts = r.ts, win = ts - ts % 60;
         uint32_t kp;
         KeyVal kv;
-        (void)key_tag(sp, P, r.row, win, kp, kv);
-        if (!key_equal(rows + (uint64_t)g * P.row_bytes, sp, P, r.row, win, kp, kv)) {
+        (void)key_tag<ENR>(sp, P, r.row, win, kp, kv);
+        if (!key_equal<ENR>(rows + (uint64_t)g * P.row_bytes, sp, P, r.row, win, kp, kv)) {
             rec_g[t] = NONE;
             collided[atomicAdd(n_collided, 1u)] = (uint32_t)t;  // rare (64-bit tag collisions)
         }
@@ -823,14 +910,18 @@ __global__ __launch_bounds__(256) void k_agg_check(const RecCtx C, const AggPara
 }
 
 // Exact re-probe of the listed records
+template <bool ENR>
 __global__ __launch_bounds__(256) void k_agg_reprobe(const RecCtx C, const AggParams P,
                                                      unsigned long long *__restrict__ tags, uint8_t *__restrict__ rows,
                                                      uint32_t *__restrict__ rec_g, const uint32_t *__restrict__ list,
                                                      uint32_t n_list, uint32_t *__restrict__ claims,
                                                      unsigned long long *__restrict__ n_claims,
+                                                     uint32_t *__restrict__ again, unsigned int *__restrict__ n_again,
                                                      unsigned int *__restrict__ err) {
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n_list; i += gridDim.x * blockDim.x) {
-        const uint64_t t = list[i];
+    // whole waves walk the list (wave_append's ballots need every lane)
+    for (uint32_t i0 = blockIdx.x * blockDim.x; i0 < n_list; i0 += gridDim.x * blockDim.x) {
+        const uint32_t i = i0 + threadIdx.x;
+        const uint64_t t = i < n_list ? list[i] : C.n_rec;
         const Rec r = rec_of(C, t, err);
         bool tentative = false, claimed = false;
         uint32_t g = NONE;
@@ -839,10 +930,11 @@ __global__ __launch_bounds__(256) void k_agg_reprobe(const RecCtx C, const AggPa
             const uint32_t ts = r.ts, win = ts - ts % 60;
             uint32_t kp;
             KeyVal kv;
-            const uint64_t h = key_tag(sp, P, r.row, win, kp, kv);
-            g = probe<true>(sp, P, r.row, win, kp, kv, h, tags, rows, err, &tentative, &claimed);
+            const uint64_t h = key_tag<ENR>(sp, P, r.row, win, kp, kv);
+            g = probe<true, ENR>(sp, P, r.row, win, kp, kv, h, tags, rows, err, &tentative, &claimed);
             rec_g[t] = g;
         }
+        wave_append(again, n_again, tentative, (uint32_t)t);  // met a slot being claimed: the next round
         wave_append(claims, n_claims, claimed, g);
     }
 }
@@ -923,7 +1015,7 @@ __device__ __forceinline__ void apply_push_constants(uint8_t *R, const AggParams
 // ordered classes are left to k_agg_ordered.
 constexpr int CN = 64;
 constexpr int CN_PROBES = 8;  // a group's entry sits within this many slots of its home slot
-template <int MAXV>  // aggregated fields held in registers (value loads issued together, before any atomic)
+template <int MAXV, bool ENR>  // aggregated fields held in registers (value loads issued together, before any atomic)
 __global__ __launch_bounds__(256, 4) void k_agg_apply(const RecCtx C, const AggParams P,
                                                     uint32_t *__restrict__ rec_g, uint8_t *__restrict__ rows,
                                                     const uint32_t *__restrict__ list,
@@ -994,10 +1086,11 @@ __global__ __launch_bounds__(256, 4) void k_agg_apply(const RecCtx C, const AggP
         }
         uint64_t xv[MAXV];
         uint32_t hv = 0, hb = 0;  // aggregated fields present: numeric (in xv) / byte-wise OR
+        const uint32_t rvp = valid ? row_vp<ENR>(sp, row) : 0u;  // enriched push: the row's presence word
 #pragma unroll
         for (int v = 0; v < MAXV; ++v) {
             xv[v] = 0;
-            if (valid && v < (int)P.n_vals && sp.val_col[v] && !vc_ordered(P.val_vc[v])) {
+            if (valid && v < (int)P.n_vals && sp.val_col[v] && (!ENR || ((rvp >> v) & 1)) && !vc_ordered(P.val_vc[v])) {
                 if (P.val_vc[v] == VC_BYTES) hb |= 1u << v;
                 else { xv[v] = value_operand(sp, P, v, row); hv |= 1u << v; }
             }
@@ -1222,7 +1315,7 @@ enum : uint8_t { U_SRC_ONE = 8, U_SRC_COLL = 9, U_SRC_PORT = 10, U_SRC_TPL = 11,
 // k_agg_apply's atomics, which run after this kernel.  The owner test costs no read of its own
 // (5-tuple: 3.3 ms of k_agg_apply per 10^8 records saved).  !FUSED (NGZ_AGG_OWN_SPLIT): runs
 // after k_agg_apply, which tested every record's owner word and applied the others.
-template <bool FUSED>
+template <bool FUSED, bool ENR>
 __global__ __launch_bounds__(256) void k_agg_apply_own(const RecCtx C, const AggParams P,
                                                        uint32_t *__restrict__ rec_g, uint8_t *__restrict__ rows,
                                                        uint32_t *__restrict__ rest, unsigned int *__restrict__ n_rest,
@@ -1263,10 +1356,11 @@ __global__ __launch_bounds__(256) void k_agg_apply_own(const RecCtx C, const Agg
             const AggSlotPlan &sp = su != NONE ? C.plans[su] : C.plans[r.slot];
             const uint32_t db = (r.info >> 2) & 0x7F;
             uint32_t hv = 0;
+            const uint32_t rvp = r.valid ? row_vp<ENR>(sp, r.row) : 0u;
 #pragma unroll
             for (int v = 0; v < 8; ++v) {
                 uint64_t x = 0;
-                if (r.valid && v < (int)P.n_vals && sp.val_col[v] && !vc_ordered(P.val_vc[v])) {
+                if (r.valid && v < (int)P.n_vals && sp.val_col[v] && (!ENR || ((rvp >> v) & 1)) && !vc_ordered(P.val_vc[v])) {
                     x = value_operand(sp, P, v, r.row);
                     hv |= 1u << v;
                 }
@@ -1387,6 +1481,7 @@ __device__ __forceinline__ bool take_new(uint8_t op, int cmp_cur_new) {
 
 // One thread per group present in the sorted record list: the ordered reductions folded in
 // record order (the stable sort kept it within a group), from the group's value.
+template <bool ENR>
 __global__ __launch_bounds__(256) void k_agg_ordered(const RecCtx C, const AggParams P,
                                                      const uint32_t *__restrict__ sg, const uint32_t *__restrict__ sr,
                                                      uint64_t n, uint8_t *__restrict__ rows,
@@ -1414,8 +1509,8 @@ __global__ __launch_bounds__(256) void k_agg_ordered(const RecCtx C, const AggPa
                     const Rec r = rec_of(C, sr[j], err);
                     if (!r.valid) continue;
                     const AggSlotPlan &sp = C.plans[r.slot];
-                    if (!sp.val_col[v]) continue;
-                    const Span s = val_span(sp, v, r.row);
+                    if (!sp.val_col[v] || (ENR && !((row_vp<ENR>(sp, r.row) >> v) & 1))) continue;
+                    const Span s = val_span<ENR>(sp, v, r.row);
                     if (!have) {
                         bval_write(dst, s, P, err);  // the group's first value, tail included
                         n0 = s.n;
@@ -1449,8 +1544,8 @@ __global__ __launch_bounds__(256) void k_agg_ordered(const RecCtx C, const AggPa
                     const Rec r = rec_of(C, sr[j], err);
                     if (!r.valid) continue;
                     const AggSlotPlan &sp = C.plans[r.slot];
-                    if (!sp.val_col[v]) continue;
-                    const Span s = val_span(sp, v, r.row);
+                    if (!sp.val_col[v] || (ENR && !((row_vp<ENR>(sp, r.row) >> v) & 1))) continue;
+                    const Span s = val_span<ENR>(sp, v, r.row);
                     const BRef x{s.p, nullptr, s.n, s.n};
                     if (!have || take_new(op, bytes_cmp(best, x))) {
                         best = x;
@@ -1477,7 +1572,7 @@ __global__ __launch_bounds__(256) void k_agg_ordered(const RecCtx C, const AggPa
                 const Rec r = rec_of(C, sr[j], err);
                 if (!r.valid) continue;
                 const AggSlotPlan &sp = C.plans[r.slot];
-                if (!sp.val_col[v]) continue;
+                if (!sp.val_col[v] || (ENR && !((row_vp<ENR>(sp, r.row) >> v) & 1))) continue;
                 const uint8_t *cell = sp.val_col[v] + r.row * sp.val_w[v];
                 if (vc == VC_F64) {
                     double x;
@@ -1980,7 +2075,7 @@ __global__ __launch_bounds__(256) void k_agg_lc_sets(const ngz_set_info *__restr
             } else {
                 const uint16_t info = dginfo[si.dgram];
                 if (info & DG_LATE) {
-                    late_n = si.n;
+                    if (!plans[si.slot].dropped) late_n = si.n;  // enriched push: dropped records are no items
                 } else if ((info & DG_USE) && plans[si.slot].usable) {
                     const ngz_dgram_hdr &h = hdr[si.dgram];
                     d.ts = h.time;
@@ -2551,21 +2646,23 @@ __global__ void k_agg_rehash(const unsigned long long *__restrict__ tags, const 
 // Tail bytes a push can write at most: need[0] the tails of every present BVAL key and value of
 // every valid record, need[1] the longest one (a group's claim writes one tail per key field, its
 // ordered fold at most one per value field, so a push writes at most slots x fields x longest)
+template <bool ENR>
 __global__ void k_agg_tail_need(const RecCtx C, const AggParams P, unsigned long long *__restrict__ need) {
     uint64_t mine = 0, longest = 0;
     for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < C.n_rec; t += (uint64_t)gridDim.x * blockDim.x) {
         const Rec r = rec_of(C, t, nullptr);
         if (!r.valid) continue;
         const AggSlotPlan &sp = C.plans[r.slot];
+        const uint32_t rkp = row_kp<ENR>(sp, r.row), rvp = row_vp<ENR>(sp, r.row);
         for (uint32_t k = 0; k < P.n_keys; ++k)
-            if (P.key_kind[k] == KK_BYTES && sp.key_col[k]) {
-                const Span s = key_span(sp, P, k, r.row);
+            if (P.key_kind[k] == KK_BYTES && sp.key_col[k] && (!ENR || ((rkp >> k) & 1))) {
+                const Span s = key_span<ENR>(sp, P, k, r.row);
                 mine += tail_span(s.n);
                 longest = max(longest, tail_span(s.n));
             }
         for (uint32_t v = 0; v < P.n_vals; ++v)
-            if ((P.val_vc[v] == VC_VBYTES || P.val_vc[v] == VC_VLIST) && sp.val_col[v]) {
-                const Span s = val_span(sp, v, r.row);
+            if ((P.val_vc[v] == VC_VBYTES || P.val_vc[v] == VC_VLIST) && sp.val_col[v] && (!ENR || ((rvp >> v) & 1))) {
+                const Span s = val_span<ENR>(sp, v, r.row);
                 mine += tail_span(s.n);
                 longest = max(longest, tail_span(s.n));
             }
@@ -2622,6 +2719,8 @@ struct ngz_agg {
     int device = 0;
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    hipEvent_t ev_r0 = nullptr, ev_r1 = nullptr;  // round the resolve launches of an enriched push
+    float t_resolve = 0;
     std::string last_error;
     bool poisoned = false;
     std::vector<ngz_agg_field> keys, vals;
@@ -2669,6 +2768,9 @@ struct ngz_agg {
     uint32_t *rank_maps = nullptr;  // one 65536-bit map per VC_RANK sub-registry value
     AggSlotPlan *plans = nullptr;
     uint32_t plans_cap = 0;
+    // ngz_agg_push_enriched: the writer id, the rows' presence words and the resolved columns of a push
+    uint8_t *enr_buf = nullptr;
+    uint64_t enr_cap = 0;
     // scratch, grown on demand
     void *scratch = nullptr;
     size_t scratch_cap = 0;
@@ -3179,6 +3281,8 @@ int ngz_agg_create(int device, const ngz_agg_field *fields, uint32_t n_fields, u
     if (hipStreamCreateWithFlags(&a->stream, hipStreamNonBlocking) != hipSuccess) return bail(NGZ_E_DEVICE, "stream");
     hipEventCreate(&a->ev0);
     hipEventCreate(&a->ev1);
+    hipEventCreate(&a->ev_r0);
+    hipEventCreate(&a->ev_r1);
     if (hipMalloc(&a->tags, slots * 8) != hipSuccess || hipMalloc(&a->rows, slots * P.row_bytes) != hipSuccess ||
         hipMalloc(&a->ident, P.row_bytes) != hipSuccess || hipMalloc(&a->dom_dict, DOM_SLOTS * 8) != hipSuccess ||
         hipMalloc(&a->newdom, NEWDOM_SLOTS * 8) != hipSuccess || hipMalloc(&a->err, 4) != hipSuccess ||
@@ -3239,6 +3343,7 @@ void ngz_agg_destroy(ngz_agg *a) {
     hipFree(a->cut);
     hipFree(a->rank_maps);
     hipFree(a->plans);
+    hipFree(a->enr_buf);
     hipFree(a->scratch);
     hipFree(a->rec_buf);
     hipFree(a->part_buf);
@@ -3247,6 +3352,8 @@ void ngz_agg_destroy(ngz_agg *a) {
     hipFree(a->lc_sets);
     if (a->ev0) hipEventDestroy(a->ev0);
     if (a->ev1) hipEventDestroy(a->ev1);
+    if (a->ev_r0) hipEventDestroy(a->ev_r0);
+    if (a->ev_r1) hipEventDestroy(a->ev_r1);
     if (a->stream) hipStreamDestroy(a->stream);
     delete a;
 }
@@ -3271,11 +3378,27 @@ int ngz_agg_layout(ngz_agg *a, uint32_t *row_bytes, uint32_t *key_off, uint16_t 
     return NGZ_OK;
 }
 
-int ngz_agg_push(ngz_agg *a, ngz_ctx *ctx, const ngz_batch_out *out, const ngz_peer *peer,
-                 int64_t collection_time_ms, uint64_t *late_records, void *hip_stream) {
+// A record kernel's launch: its per-row instantiation (ENR) only in an enriched push with a field on
+// an added or resolved column; every other push launches the code without the presence loads
+#define AGG_LAUNCH_ENR(K, ...)                                      \
+    do {                                                            \
+        if (enr_rows) hipLaunchKernelGGL((K<true>), __VA_ARGS__);   \
+        else hipLaunchKernelGGL((K<false>), __VA_ARGS__);           \
+    } while (0)
+#define AGG_LAUNCH_ENR2(K, A, ...)                                     \
+    do {                                                               \
+        if (enr_rows) hipLaunchKernelGGL((K<A, true>), __VA_ARGS__);   \
+        else hipLaunchKernelGGL((K<A, false>), __VA_ARGS__);           \
+    } while (0)
+
+// ngz_agg_push, and with `enr` (an enricher's results for this batch) ngz_agg_push_enriched
+static int push_impl(ngz_agg *a, ngz_enrich *e, const std::vector<ngze::SlotResult> *enr, ngz_ctx *ctx,
+                     const ngz_batch_out *out, const ngz_peer *peer, int64_t collection_time_ms,
+                     uint64_t *late_records, void *hip_stream) {
     if (!a || !ctx || !out || !peer || (peer->family != 4 && peer->family != 6)) return NGZ_E_INVALID;
     if (late_records) *late_records = 0;
     a->last_path = "none";  // no record to reduce (set below otherwise)
+    a->t_resolve = 0;
     if (a->poisoned) return fail(a, NGZ_AGG_E_POISONED, "aggregator failed earlier: ngz_agg_reset it");
     AGG_HIP(a, hipSetDevice(a->device));
     if (hip_stream) AGG_HIP(a, hipStreamSynchronize((hipStream_t)hip_stream));
@@ -3349,41 +3472,156 @@ int ngz_agg_push(ngz_agg *a, ngz_ctx *ctx, const ngz_batch_out *out, const ngz_p
     const uint32_t S = out->n_slots;
     std::vector<AggSlotPlan> plans(std::max<uint32_t>(S, 1));
     std::vector<ngz_field_info> fi;
+    // enriched push: the slots with a resolve pass, and what of the aggregator's scratch they use
+    // (offsets into enr_buf until it is sized; the writer id sits at its start)
+    struct EnrSlot {
+        uint32_t slot;
+        ngza::ResolvePlan rp;
+        uint64_t kpres_off, vpres_off;
+        bool sel_scratch[ngza::RS_MAX_SEL];  // the field has a resolved column, at sel_off
+        uint64_t sel_off[ngza::RS_MAX_SEL];
+    };
+    struct EnrFix {  // a plan column in the scratch
+        uint32_t slot, index;
+        bool is_value;
+        uint64_t off;
+    };
+    std::vector<EnrSlot> enr_slots;
+    std::vector<EnrFix> enr_fix;
+    const std::string writer = enr ? std::string(ngz_enrich_writer_id(e)) : std::string();
+    auto al256 = [](uint64_t x) { return (x + 255) & ~255ull; };
+    uint64_t enr_need = al256(writer.size() + 1);
+    const uint8_t *enr_arena = nullptr;
+    if (enr) ngz_enrich_value_arena(e, &enr_arena, nullptr, nullptr);
+    std::vector<ngz_agg_slot_field> sfields;
+    std::vector<ngz_agg_ref> srefs;
     for (uint32_t s = 0; s < S; ++s) {
         AggSlotPlan &sp = plans[s];
         memset(&sp, 0, sizeof sp);
         const ngz_slot_info &si = out->slots[s];
         sp.proto = si.proto;
         sp.bytes = ctx->last_in.bytes;
+        const ngze::SlotResult *er = enr && s < enr->size() ? &(*enr)[s] : nullptr;
+        if (er && er->dropped) {  // records with scope fields are no items (actor.rs:178, :237)
+            sp.dropped = 1;
+            continue;
+        }
         if (!si.n_records || !si.columns) continue;
         const int nf = ngz_slot_fields(ctx, s, nullptr, 0);
         if (nf < 0) { restore(); return fail(a, NGZ_E_INVALID, "ngz_slot_fields"); }
         fi.resize(std::max(nf, 1));
         ngz_slot_fields(ctx, s, fi.data(), (uint32_t)nf);
+        if (er) {
+            if (er->rows != si.n_records || er->cols.size() > NGZ_AGG_ENRICH_MAX_COLUMNS) {
+                restore();
+                return fail(a, NGZ_E_INVALID, "the enricher's results do not match the batch");
+            }
+            sfields.resize(std::max(nf, 1));
+            for (int i = 0; i < nf; ++i) sfields[i] = ngz_agg_slot_field{fi[i].pen, fi[i].ie_id, (uint8_t)(fi[i].is_scope ? 1 : 0), 0};
+            srefs.resize(std::max<size_t>(er->cols.size(), 1));
+            for (size_t c = 0; c < er->cols.size(); ++c) srefs[c] = ngz_agg_ref{er->cols[c].pen, er->cols[c].ie_id, er->cols[c].index};
+        }
+        int es = -1;  // the slot's entry of enr_slots, once a field needs the resolve pass
+        uint32_t own_keys = 0, own_vals = 0;  // enriched push: the selected fields on the template's own columns
+        // Where a selected field's column is: the template's own (ngz_agg_push), or with the
+        // enrichment an added column read in place, or a resolved column of the scratch
+        struct Loc {
+            bool found = false;
+            uint8_t kind = 0;
+            uint32_t width = 0;
+            const uint8_t *col = nullptr;
+            bool scratch = false;
+        };
+        auto locate = [&](const ngz_agg_field &f, bool is_value, uint32_t index, Loc &L) -> int {
+            if (!er) {
+                uint32_t seen = 0;
+                for (int i = 0; i < nf; ++i) {
+                    if (fi[i].is_scope) continue;
+                    if (fi[i].pen == f.pen && fi[i].ie_id == f.ie_id) {
+                        if (seen == f.index) {
+                            L = Loc{true, fi[i].kind, fi[i].width, si.columns + (uint64_t)si.capacity * fi[i].col_off, false};
+                            return NGZ_OK;
+                        }
+                        ++seen;
+                    }
+                }
+                return NGZ_OK;
+            }
+            ngz_agg_enrich_resolution res;
+            if (ngza::resolve_field(sfields.data(), (uint32_t)nf, srefs.data(), (uint32_t)er->cols.size(), f.pen, f.ie_id,
+                                    f.index, &res))
+                return fail(a, NGZ_E_LIMIT, "more added columns than the aggregation takes");
+            if (res.kind == NGZ_AGG_RES_NONE) return NGZ_OK;
+            if (res.kind == NGZ_AGG_RES_OWN) {
+                const ngz_field_info &o = fi[res.own_field];
+                L = Loc{true, o.kind, o.width, si.columns + (uint64_t)si.capacity * o.col_off, false};
+                (is_value ? own_vals : own_keys) |= 1u << index;
+                return NGZ_OK;
+            }
+            if (es < 0) {
+                es = (int)enr_slots.size();
+                enr_slots.emplace_back();
+                EnrSlot &n = enr_slots.back();
+                memset(&n, 0, sizeof n);
+                n.slot = s;
+                n.rp.mask = er->mask;
+                n.rp.n_rows = si.n_records;
+                for (size_t c = 0; c < er->cols.size(); ++c) n.rp.col[c] = er->cols[c].data;
+                n.kpres_off = enr_need;
+                enr_need += al256(4ull * si.n_records);
+                n.vpres_off = enr_need;
+                enr_need += al256(4ull * si.n_records);
+            }
+            EnrSlot &n = enr_slots[es];
+            ngza::ResolveSel &sl = n.rp.sel[n.rp.n_sel];
+            sl.bit = (uint8_t)index;
+            sl.is_value = is_value ? 1 : 0;
+            sl.ordinal = res.ordinal;
+            sl.writer_after = res.kind == NGZ_AGG_RES_WRITER || res.writer_after;
+            sl.wid_len = (uint32_t)writer.size();
+            for (uint32_t c = 0; c < res.n_candidates; ++c) sl.cand |= 1u << res.candidates[c];
+            L.found = true;
+            if (res.kind == NGZ_AGG_RES_ADDED && res.n_candidates == 1 && !res.writer_after) {
+                const ngz_enrich_column &c = er->cols[res.candidates[0]];  // read in place
+                L.kind = c.kind;
+                L.width = c.width;
+                L.col = c.data;
+            } else {  // several candidates or the writer id: the chosen cell in a resolved column
+                L.kind = NGZ_K_VLEN;
+                L.width = 16;
+                for (uint32_t c = 0; c < res.n_candidates; ++c) {
+                    const ngz_enrich_column &col = er->cols[res.candidates[c]];
+                    if (c == 0 && !sl.writer_after) {
+                        L.kind = col.kind;
+                        L.width = col.width;
+                    }
+                    if (col.kind != L.kind || col.width != L.width)
+                        return fail(a, NGZ_E_LIMIT, "added columns of one IE that differ in kind or width");
+                }
+                sl.width = L.width;
+                n.sel_scratch[n.rp.n_sel] = true;
+                n.sel_off[n.rp.n_sel] = enr_need;
+                enr_fix.push_back(EnrFix{s, index, is_value, enr_need});
+                enr_need += al256((uint64_t)L.width * (((uint64_t)si.n_records + 3) & ~3ull));
+                L.scratch = true;  // the column's address follows once the scratch is sized (enr_fix)
+            }
+            if (L.kind == NGZ_K_VLEN) (is_value ? sp.val_ext : sp.key_ext) |= 1u << index;
+            ++n.rp.n_sel;
+            return NGZ_OK;
+        };
         int tbit;
         if (int r = put(a->templates, ((int64_t)si.proto << 16) | si.template_id, SET_BITS, tbit)) { restore(); return r; }
         if (tbit < 0) { restore(); return fail(a, NGZ_AGG_E_OVERFLOW, "more than 64 template ids in live windows"); }
         sp.tpl_bit = 1ull << tbit;
-        auto find_field = [&](const ngz_agg_field &f) -> int {
-            uint32_t seen = 0;
-            for (int i = 0; i < nf; ++i) {
-                if (fi[i].is_scope) continue;
-                if (fi[i].pen == f.pen && fi[i].ie_id == f.ie_id) {
-                    if (seen == f.index) return i;
-                    ++seen;
-                }
-            }
-            return -1;
-        };
         for (uint32_t k = 0; k < a->P.n_keys; ++k) {
-            const int i = find_field(a->keys[k]);
-            if (i < 0) continue;
-            const ngz_field_info &f = fi[i];
+            Loc f;
+            if (int r = locate(a->keys[k], false, k, f)) { restore(); return r; }
+            if (!f.found) continue;
             if (a->P.key_kind[k] == KK_BYTES) {
                 // any length, fixed or variable-length (a record's text / bytes, BVAL)
                 if (f.kind == NGZ_K_FAIL) { restore(); return fail(a, NGZ_E_LIMIT, "key field of a failing template"); }
                 if (f.kind == NGZ_K_VLEN) sp.key_vlen |= 1u << k;
-                sp.key_col[k] = si.columns + (uint64_t)si.capacity * f.col_off;
+                sp.key_col[k] = f.col;
                 sp.key_w[k] = f.width;
                 if (a->key_w[k] < 0) a->key_w[k] = f.width;
                 if (a->key_kind_seen[k] < 0) a->key_kind_seen[k] = f.kind;
@@ -3398,22 +3636,22 @@ int ngz_agg_push(ngz_agg *a, ngz_ctx *ctx, const ngz_batch_out *out, const ngz_p
                 restore();
                 return fail(a, NGZ_E_LIMIT, "key column width differs from the IE's width");
             }
-            sp.key_col[k] = si.columns + (uint64_t)si.capacity * f.col_off;
+            sp.key_col[k] = f.col;
             sp.key_w[k] = f.width;
             if (a->key_w[k] < 0) a->key_w[k] = f.width;
             if (a->key_kind_seen[k] < 0) a->key_kind_seen[k] = f.kind;
         }
         for (uint32_t v = 0; v < a->P.n_vals; ++v) {
-            const int i = find_field(a->vals[v]);
-            if (i < 0) continue;
-            const ngz_field_info &f = fi[i];
+            Loc f;
+            if (int r = locate(a->vals[v], true, v, f)) { restore(); return r; }
+            if (!f.found) continue;
             const int vc = a->P.val_vc[v];
             if ((vc == VC_VBYTES || vc == VC_VLIST) && f.kind != NGZ_K_FAIL) {
                 // Box<[u8]> values: any length, fixed or variable-length (BVAL)
                 if (f.kind == NGZ_K_VLEN) sp.val_vlen |= 1u << v;
                 if (a->val_w[v] < 0) a->val_w[v] = f.width;
                 if (a->val_kind_seen[v] < 0) a->val_kind_seen[v] = f.kind;
-                sp.val_col[v] = si.columns + (uint64_t)si.capacity * f.col_off;
+                sp.val_col[v] = f.col;
                 sp.val_w[v] = f.width;
                 continue;
             }
@@ -3434,13 +3672,41 @@ int ngz_agg_push(ngz_agg *a, ngz_ctx *ctx, const ngz_batch_out *out, const ngz_p
             }
             a->val_w[v] = f.width;
             if (a->val_kind_seen[v] < 0) a->val_kind_seen[v] = f.kind;
-            sp.val_col[v] = si.columns + (uint64_t)si.capacity * f.col_off;
+            sp.val_col[v] = f.col;
             sp.val_w[v] = f.width;
         }
         sp.usable = 1;
+        if (es >= 0) {  // the fields on own columns are present in every row
+            ngza::ResolvePlan &rp = enr_slots[es].rp;
+            rp.own_keys = own_keys;
+            rp.own_vals = own_vals;
+            sp.xbytes = enr_arena;
+        }
     }
     const uint32_t D = out->n_dgrams, NS = out->n_sets;
     if (!D || !NS) return NGZ_OK;
+    const bool enr_rows = !enr_slots.empty();  // some selected field is per row: the ENR kernels, the general path
+    if (enr_rows) {
+        // the aggregator's scratch for this push: the writer id, the presence words, the resolved columns
+        if (enr_need > a->enr_cap) {
+            hipFree(a->enr_buf);
+            a->enr_buf = nullptr;
+            a->enr_cap = 0;
+            if (hipMalloc(&a->enr_buf, enr_need) != hipSuccess) { restore(); return fail(a, NGZ_E_NOMEM, "enrichment scratch"); }
+            a->enr_cap = enr_need;
+        }
+        for (EnrSlot &n : enr_slots) {
+            n.rp.kpres = (uint32_t *)(a->enr_buf + n.kpres_off);
+            n.rp.vpres = (uint32_t *)(a->enr_buf + n.vpres_off);
+            for (uint32_t i = 0; i < n.rp.n_sel; ++i)
+                if (n.sel_scratch[i]) n.rp.sel[i].resolved = a->enr_buf + n.sel_off[i];
+            AggSlotPlan &sp = plans[n.slot];
+            sp.kpres = n.rp.kpres;
+            sp.vpres = n.rp.vpres;
+            sp.wid = a->enr_buf;
+        }
+        for (const EnrFix &f : enr_fix) (f.is_value ? plans[f.slot].val_col : plans[f.slot].key_col)[f.index] = a->enr_buf + f.off;
+    }
     // scratch: has_rec[D], ts[D], pm[D], dginfo[D], cnt/rstart[NS+1], cub temp
     size_t cub_max = 0, cub_sum = 0;
     hipcub::DeviceScan::InclusiveScan(nullptr, cub_max, (uint32_t *)nullptr, (uint32_t *)nullptr, hipcub::Max(), D,
@@ -3491,7 +3757,19 @@ int ngz_agg_push(ngz_agg *a, ngz_ctx *ctx, const ngz_batch_out *out, const ngz_p
     AGG_HIP(a, hipMemsetAsync(a->n_claims, 0, 8, st));
     const ngz_dgram_hdr *hdr = out->dgrams;
     const ngz_set_info *sets = out->sets;
-    hipLaunchKernelGGL(k_agg_dgram, dim3(grid_for(NS)), dim3(256), 0, st, sets, NS, D, has_rec);
+    if (enr_rows) {
+        // resolve pass: one launch per slot in which a selected field lands past the template's own columns
+        if (!writer.empty())
+            AGG_HIP(a, hipMemcpyAsync(a->enr_buf, writer.data(), writer.size(), hipMemcpyHostToDevice, st));
+        AGG_HIP(a, hipEventRecord(a->ev_r0, st));
+        for (const EnrSlot &n : enr_slots)
+            if (ngza::resolve_launch(n.rp, st)) { restore(); return fail(a, NGZ_E_DEVICE, "resolve pass launch"); }
+        AGG_HIP(a, hipEventRecord(a->ev_r1, st));
+    }
+    if (enr)
+        hipLaunchKernelGGL(k_agg_dgram_kept, dim3(grid_for(NS)), dim3(256), 0, st, sets, NS, D, a->plans, S, has_rec);
+    else
+        hipLaunchKernelGGL(k_agg_dgram, dim3(grid_for(NS)), dim3(256), 0, st, sets, NS, D, has_rec);
     hipLaunchKernelGGL(k_agg_ts, dim3(grid_for(D)), dim3(256), 0, st, hdr, has_rec, D, ts);
     size_t tmp = cub_max;
     AGG_HIP(a, hipcub::DeviceScan::InclusiveScan(cub_tmp, tmp, ts, pm, hipcub::Max(), D, st));
@@ -3580,7 +3858,7 @@ int ngz_agg_push(ngz_agg *a, ngz_ctx *ctx, const ngz_batch_out *out, const ngz_p
     // straight to the general path (high-cardinality keys pay for one try in 16)
     const bool lc_try = lc_now == 1 || (lc_now != 0 && n_rec >= (1u << 16) && (a->lc_skip == 0 || --a->lc_skip == 0));
     if (n_rec && P.packed && P.lds_ok && P.n_vals <= (uint32_t)LC_MAXV && P.n_keys <= (uint32_t)LC_MAXK &&
-        !ordered && lc_try) {
+        !ordered && lc_try && !enr_rows) {
         // one-wave workgroups; the lane-private LDS cells of LC_NK tuples bound the residency
         // (160 KB per CU): a grid of that many workgroups, a multiple of the 8 XCDs
         const size_t lds = lc_lds_bytes(P.n_vals);
@@ -3657,7 +3935,7 @@ int ngz_agg_push(ngz_agg *a, ngz_ctx *ctx, const ngz_batch_out *out, const ngz_p
         // groups reserve 2 slots per group's worth, not 3 GB)
         unsigned long long nd[2] = {0, 0};
         AGG_HIP(a, hipMemsetAsync(a->arena_used + 1, 0, 16, st));
-        hipLaunchKernelGGL(k_agg_tail_need, dim3(grid_for(n_rec, 256, 4096)), dim3(256), 0, st, C, P, a->arena_used + 1);
+        AGG_LAUNCH_ENR(k_agg_tail_need, dim3(grid_for(n_rec, 256, 4096)), dim3(256), 0, st, C, P, a->arena_used + 1);
         AGG_HIP(a, hipMemcpyAsync(nd, a->arena_used + 1, 16, hipMemcpyDeviceToHost, st));
         AGG_HIP(a, hipStreamSynchronize(st));
         uint32_t n_bval = 0;
@@ -3672,7 +3950,7 @@ int ngz_agg_push(ngz_agg *a, ngz_ctx *ctx, const ngz_batch_out *out, const ngz_p
     const uint32_t fg = std::max<uint32_t>(1, std::min<uint32_t>(blocks, 1u << 20));
     if (n_rec) {
         AGG_HIP(a, hipMemsetAsync(a->n_coll, 0, 4, st));
-        hipLaunchKernelGGL(k_agg_claim, dim3(fg), dim3(256), 0, st, C, P, a->tags, a->rows, rec_g, claims, a->n_claims,
+        AGG_LAUNCH_ENR(k_agg_claim, dim3(fg), dim3(256), 0, st, C, P, a->tags, a->rows, rec_g, claims, a->n_claims,
                            a->late, list_b, a->n_coll, a->err);
         if (!P.packed) {
             // hashed keys: the records that took a slot another record of this pass claimed are
@@ -3683,7 +3961,7 @@ int ngz_agg_push(ngz_agg *a, ngz_ctx *ctx, const ngz_batch_out *out, const ngz_p
             AGG_HIP(a, hipStreamSynchronize(st));
             AGG_HIP(a, hipMemsetAsync(a->n_coll, 0, 4, st));
             if (nt)
-                hipLaunchKernelGGL(k_agg_check, dim3(grid_for(nt, 256, 1u << 20)), dim3(256), 0, st, C, P, a->rows, rec_g,
+                AGG_LAUNCH_ENR(k_agg_check, dim3(grid_for(nt, 256, 1u << 20)), dim3(256), 0, st, C, P, a->rows, rec_g,
                                    list_b, nt, list_a, a->n_coll, a->err);
             for (int round = 0;; ++round) {
                 unsigned int nc = 0;
@@ -3695,10 +3973,11 @@ int ngz_agg_push(ngz_agg *a, ngz_ctx *ctx, const ngz_batch_out *out, const ngz_p
                     AGG_HIP(a, hipStreamSynchronize(st));
                     return rollback(NGZ_E_DEVICE, "key collision resolution did not converge");
                 }
-                hipLaunchKernelGGL(k_agg_reprobe, dim3(grid_for(nc)), dim3(256), 0, st, C, P, a->tags, a->rows, rec_g,
-                                   list_a, nc, claims, a->n_claims, a->err);
+                // the records that met a slot being claimed join the next round's list with the collided ones
                 AGG_HIP(a, hipMemsetAsync(a->n_coll, 0, 4, st));
-                hipLaunchKernelGGL(k_agg_check, dim3(grid_for(nc)), dim3(256), 0, st, C, P, a->rows, rec_g, list_a, nc,
+                AGG_LAUNCH_ENR(k_agg_reprobe, dim3(grid_for(nc)), dim3(256), 0, st, C, P, a->tags, a->rows, rec_g,
+                                   list_a, nc, claims, a->n_claims, list_b, a->n_coll, a->err);
+                AGG_LAUNCH_ENR(k_agg_check, dim3(grid_for(nc)), dim3(256), 0, st, C, P, a->rows, rec_g, list_a, nc,
                                    list_b, a->n_coll, a->err);
                 std::swap(list_a, list_b);
             }
@@ -3726,7 +4005,7 @@ int ngz_agg_push(ngz_agg *a, ngz_ctx *ctx, const ngz_batch_out *out, const ngz_p
         // (NGZ_AGG_OPT_PARTITION: 0 never, 1 whenever the config allows it)
         const int part_env = a->opt_partition;  // NGZ_AGG_OPT_PARTITION
         const uint64_t groups = a->live + n_claims, n_part = a->slots / PART_SLOTS;
-        const bool part_ok = P.lds_ok && P.n_vals <= 8 && a->slots >= PART_SLOTS && n_part <= 8192;
+        const bool part_ok = !enr_rows && P.lds_ok && P.n_vals <= 8 && a->slots >= PART_SLOTS && n_part <= 8192;
         const bool part = part_ok && (part_env == 1 || (part_env != 0 && n_rec >= (1u << 20) && groups > 4096 &&
                                                          groups * 8 <= (uint64_t)n_rec));
         if (part) {
@@ -3788,22 +4067,22 @@ int ngz_agg_push(ngz_agg *a, ngz_ctx *ctx, const ngz_batch_out *out, const ngz_p
 
             // owners reduce their rows first, the records k_agg_apply_own lists apply atomics after
             AGG_HIP(a, hipMemsetAsync(a->n_coll, 0, 4, st));
-            hipLaunchKernelGGL(k_agg_apply_own<true>, dim3(fg), dim3(256), 0, st, C, P, rec_g, a->rows, list_a, a->n_coll,
+            AGG_LAUNCH_ENR2(k_agg_apply_own, true, dim3(fg), dim3(256), 0, st, C, P, rec_g, a->rows, list_a, a->n_coll,
                                a->err);
             if (P.n_vals <= 8)
-                hipLaunchKernelGGL(k_agg_apply<8>, dim3(ig), dim3(256), 0, st, C, P, rec_g, a->rows, list_a, a->n_coll, a->err);
+                AGG_LAUNCH_ENR2(k_agg_apply, 8, dim3(ig), dim3(256), 0, st, C, P, rec_g, a->rows, list_a, a->n_coll, a->err);
             else
-                hipLaunchKernelGGL(k_agg_apply<NGZ_AGG_MAX_VALUES>, dim3(ig), dim3(256), 0, st, C, P, rec_g, a->rows, list_a,
+                AGG_LAUNCH_ENR2(k_agg_apply, NGZ_AGG_MAX_VALUES, dim3(ig), dim3(256), 0, st, C, P, rec_g, a->rows, list_a,
                                    a->n_coll, a->err);
         } else {
             // owner records (marked in rec_g) reduced after every other record
             if (P.n_vals <= 8)
-                hipLaunchKernelGGL(k_agg_apply<8>, dim3(ag), dim3(256), 0, st, C, P, rec_g, a->rows, nullptr, nullptr, a->err);
+                AGG_LAUNCH_ENR2(k_agg_apply, 8, dim3(ag), dim3(256), 0, st, C, P, rec_g, a->rows, nullptr, nullptr, a->err);
             else
-                hipLaunchKernelGGL(k_agg_apply<NGZ_AGG_MAX_VALUES>, dim3(ag), dim3(256), 0, st, C, P, rec_g, a->rows, nullptr,
+                AGG_LAUNCH_ENR2(k_agg_apply, NGZ_AGG_MAX_VALUES, dim3(ag), dim3(256), 0, st, C, P, rec_g, a->rows, nullptr,
                                    nullptr, a->err);
             if (P.own)
-                hipLaunchKernelGGL(k_agg_apply_own<false>, dim3(fg), dim3(256), 0, st, C, P, rec_g, a->rows, nullptr, nullptr,
+                AGG_LAUNCH_ENR2(k_agg_apply_own, false, dim3(fg), dim3(256), 0, st, C, P, rec_g, a->rows, nullptr, nullptr,
                                    a->err);
         }
         if (ordered) {
@@ -3817,7 +4096,7 @@ int ngz_agg_push(ngz_agg *a, ngz_ctx *ctx, const ngz_batch_out *out, const ngz_p
             end_bit = 32;  // NONE (all ones) must sort after every slot
             size_t tb = sort_tmp;
             AGG_HIP(a, hipcub::DeviceRadixSort::SortPairs(stmp, tb, sk, sk2, sv, sv2, (int)n_rec, 0, end_bit, st));
-            hipLaunchKernelGGL(k_agg_ordered, dim3(grid_for(n_rec)), dim3(256), 0, st, C, P, sk2, sv2, (uint64_t)n_rec,
+            AGG_LAUNCH_ENR(k_agg_ordered, dim3(grid_for(n_rec)), dim3(256), 0, st, C, P, sk2, sv2, (uint64_t)n_rec,
                                a->rows, a->err);
         }
     }
@@ -3842,10 +4121,31 @@ done:
         }
     }
     hipEventElapsedTime(&a->t_push, a->ev0, a->ev1);
+    a->t_resolve = 0;
+    if (enr_rows) hipEventElapsedTime(&a->t_resolve, a->ev_r0, a->ev_r1);
     a->live += n_claims;
     if (last_pm > a->peer_time[pi]) a->peer_time[pi] = last_pm;
     if (late_records) *late_records = late;
     return NGZ_OK;
+}
+
+int ngz_agg_push(ngz_agg *a, ngz_ctx *ctx, const ngz_batch_out *out, const ngz_peer *peer,
+                 int64_t collection_time_ms, uint64_t *late_records, void *hip_stream) {
+    return push_impl(a, nullptr, nullptr, ctx, out, peer, collection_time_ms, late_records, hip_stream);
+}
+
+int ngz_agg_push_enriched(ngz_agg *a, ngz_enrich *e, ngz_ctx *ctx, const ngz_batch_out *out, const ngz_peer *peer,
+                          int64_t collection_time_ms, uint64_t *late_records, void *hip_stream) {
+    if (!a || !e || !ctx || !out || !peer) return NGZ_E_INVALID;
+    if (late_records) *late_records = 0;
+    if (ngze::enrich_device(e) != a->device) return fail(a, NGZ_E_INVALID, "the enricher is on another device");
+    if (ctx->device != a->device) return fail(a, NGZ_E_INVALID, "the context is on another device");
+    if (ctx->async.pending.load()) return fail(a, NGZ_E_INVALID, "a submitted decode is pending on the context");
+    // the check behind ngz_enrich_slot_columns: the enricher's results are of ctx's last decode
+    const std::vector<ngze::SlotResult> *res = ngze::results_for(e, ctx);
+    if (!res || res->size() != out->n_slots)
+        return fail(a, NGZ_E_INVALID, "the enricher has not applied the context's last batch");
+    return push_impl(a, e, res, ctx, out, peer, collection_time_ms, late_records, hip_stream);
 }
 
 int64_t ngz_agg_groups(ngz_agg *a) {
@@ -3981,6 +4281,12 @@ int ngz_agg_set_option(ngz_agg *a, int opt, int64_t value) {
 int ngz_agg_last_timing(ngz_agg *a, float *push_ms) {
     if (!a) return NGZ_E_INVALID;
     if (push_ms) *push_ms = a->t_push;
+    return NGZ_OK;
+}
+
+int ngz_agg_last_resolve_timing(ngz_agg *a, float *resolve_ms) {
+    if (!a || !resolve_ms) return NGZ_E_INVALID;
+    *resolve_ms = a->t_resolve;
     return NGZ_OK;
 }
 
