@@ -18,6 +18,8 @@
 #include "ngz_enrich_internal.h"
 #include "ngz_host.h"
 #include "ngz_renorm_internal.h"
+#include "ngz_stage.h"
+#include "ngz_template_record.h"
 
 namespace {
 
@@ -90,12 +92,6 @@ __host__ __device__ inline uint32_t en_hash(uint32_t map, const uint4 *key, uint
     return h;
 }
 
-__device__ __forceinline__ uint64_t en_wave_sum(uint64_t v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-
 __device__ __forceinline__ uint32_t en_word(const uint4 &v, uint32_t i) {
     return i == 0 ? v.x : i == 1 ? v.y : i == 2 ? v.z : v.w;
 }
@@ -107,15 +103,10 @@ __device__ __forceinline__ void en_load4(const uint8_t *col, uint32_t w, uint32_
     const uint8_t *p = col + (uint64_t)w * r0;
 #pragma unroll
     for (int j = 0; j < 4; ++j) v[j] = make_uint4(0, 0, 0, 0);
-    if (w == 4) {
-        const uint4 x = *(const uint4 *)p;
-        v[0].x = x.x; v[1].x = x.y; v[2].x = x.z; v[3].x = x.w;
-    } else if (w == 2) {
-        const uint2 x = *(const uint2 *)p;
-        v[0].x = x.x & 0xFFFFu; v[1].x = x.x >> 16; v[2].x = x.y & 0xFFFFu; v[3].x = x.y >> 16;
-    } else if (w == 1) {
-        const uint32_t x = *(const uint32_t *)p;
-        v[0].x = x & 0xFFu; v[1].x = (x >> 8) & 0xFFu; v[2].x = (x >> 16) & 0xFFu; v[3].x = x >> 24;
+    if (w == 4 || w == 2 || w == 1) {
+        uint32_t x[4];
+        ngzs::load4(col, w, r0, x);
+        v[0].x = x[0]; v[1].x = x[1]; v[2].x = x[2]; v[3].x = x[3];
     } else if (w == 8) {
         const uint4 a = *(const uint4 *)p, b = *(const uint4 *)(p + 16);
         v[0].x = a.x; v[0].y = a.y; v[1].x = a.z; v[1].y = a.w;
@@ -181,8 +172,6 @@ __device__ __forceinline__ uint32_t en_probe(const EnShape &S, const EnEntry *__
 
 __global__ __launch_bounds__(EN_THREADS) void k_enrich(const EnPlan P) {
     __shared__ unsigned long long acc[EN_STATS];
-    if (threadIdx.x < EN_STATS) acc[threadIdx.x] = 0;
-    __syncthreads();
     uint32_t n_matched = 0, n_added = 0;
     const uint32_t quads = (P.n_rows + EN_ROWS_PER_LANE - 1) / EN_ROWS_PER_LANE;
     for (uint32_t q = blockIdx.x * EN_THREADS + threadIdx.x; q < quads; q += gridDim.x * EN_THREADS) {
@@ -254,16 +243,12 @@ __global__ __launch_bounds__(EN_THREADS) void k_enrich(const EnPlan P) {
             n_added += __popc(mask[j]);
         }
     }
-    const uint64_t s0 = en_wave_sum(n_matched), s1 = en_wave_sum(n_added);
-    if ((threadIdx.x & 63) == 0) {
-        if (s0) atomicAdd(&acc[0], (unsigned long long)s0);
-        if (s1) atomicAdd(&acc[1], (unsigned long long)s1);
-    }
-    __syncthreads();
-    if (threadIdx.x < EN_STATS && acc[threadIdx.x]) atomicAdd(&P.stats[threadIdx.x], acc[threadIdx.x]);
+    const uint64_t cnt[EN_STATS] = {n_matched, n_added};
+    unsigned long long *const dst[EN_STATS] = {&P.stats[0], &P.stats[1]};
+    ngzs::block_add<EN_STATS>(acc, cnt, dst);
 }
 
-// One thread per data set, as k_renorm_sets: the rows of a set whose message decoded get the byte
+// One thread per data set (ngzs::for_each_set): the rows of a set whose message decoded get the byte
 // 1 (the peer has no map for the message's observation domain) or 2 + i (its i-th domain, sorted);
 // rows of failed messages keep the 0 the buffer was cleared to and are counted per slot.  err bit
 // 0: a set outside the batch's tables.
@@ -272,17 +257,11 @@ __global__ void k_enrich_sets(const ngz_set_info *__restrict__ sets, uint32_t n_
                               const uint64_t *__restrict__ row_off, uint8_t *__restrict__ rowdom,
                               const uint32_t *__restrict__ domains, uint32_t n_domains,
                               unsigned long long *__restrict__ bad_rows, unsigned int *__restrict__ err) {
-    for (uint32_t s = blockIdx.x * blockDim.x + threadIdx.x; s < n_sets; s += gridDim.x * blockDim.x) {
-        const ngz_set_info si = sets[s];
-        if (!si.n) continue;
-        if (si.dgram >= n_dgrams || si.slot >= n_slots || (uint64_t)si.rec0 + si.n > slot_rows[si.slot]) {
-            atomicOr(err, 1u);
-            continue;
-        }
-        const ngz_dgram_hdr h = hdr[si.dgram];
+    ngzs::for_each_set(sets, n_sets, hdr, n_dgrams, n_slots, slot_rows, err, [&](uint32_t, const ngz_set_info &si, const ngz_dgram_hdr &dh) {
+        const ngz_dgram_hdr h = dh;
         if (h.status != NGZ_DG_OK) {
             atomicAdd(&bad_rows[si.slot], (unsigned long long)si.n);
-            continue;
+            return;
         }
         uint32_t v = 1;
         uint32_t lo = 0, hi = n_domains;
@@ -298,7 +277,7 @@ __global__ void k_enrich_sets(const ngz_set_info *__restrict__ sets, uint32_t n_
         const uint32_t v4 = v * 0x01010101u;
         for (; p + 16 <= end; p += 16) *(uint4 *)p = make_uint4(v4, v4, v4, v4);
         while (p < end) *p++ = (uint8_t)v;
-    }
+    });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -361,16 +340,12 @@ uint4 pad16(const std::string &b) {
 
 }  // namespace
 
-struct ngz_enrich {
-    int device = 0;
+struct ngz_enrich : ngzs::Stage {
+    ngz_enrich() : Stage(2) {}
     std::string writer_id;
-    std::string last_error;
     ngze::Cache cache;
     ngz_enrich_stats totals{};
     int64_t table_bits = 0;  // NGZ_ENRICH_OPT_TABLE_BITS
-    bool device_ready = false;
-    int n_cus = 256;
-    hipEvent_t ev[2]{};
     float apply_ms = 0;
     std::map<ngze::PeerIp, std::unique_ptr<PeerDev>> peers;
     // value arena: the bytes of variable-length values, interned (offsets stay valid as it grows)
@@ -392,36 +367,12 @@ struct ngz_enrich {
     std::map<const ngz_ctx *, std::unique_ptr<CtxResult>> by_ctx;
     ngzh::DevBuf<uint64_t> d_meta;    // row_off[S], then slot_rows[S] as uint32_t
     ngzh::DevBuf<unsigned long long> d_counters;  // stats[EN_STATS], err, bad_rows[S]
-    uint64_t *h_meta = nullptr;                   // pinned
-    size_t h_meta_cap = 0;
-    unsigned long long *h_counters = nullptr;     // pinned
-    size_t h_counters_cap = 0;
+    ngzs::PinnedBuf<uint64_t> h_meta;
+    ngzs::PinnedBuf<unsigned long long> h_counters;
     std::vector<ngz_enrich_resolved> lookup_tmp;
 };
 
 namespace {
-
-int efail(ngz_enrich *e, int rc, const std::string &msg) {
-    if (e) e->last_error = msg;
-    return rc;
-}
-
-#define EN_HIP(e, x)                                                                            \
-    do {                                                                                        \
-        hipError_t e_ = (x);                                                                    \
-        if (e_ != hipSuccess) return efail(e, NGZ_E_DEVICE, std::string(#x) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
-template <class T>
-int pinned_reserve(T **p, size_t *cap, size_t n) {
-    if (n <= *cap) return 0;
-    if (*p) hipHostFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    if (hipHostMalloc((void **)p, n * sizeof(T), hipHostMallocDefault) != hipSuccess) return -1;
-    *cap = n;
-    return 0;
-}
 
 // Is the IE of a scope field one whose canonical encoding compares as the reference's Field does
 bool scope_ie_ok(const ngz_enrich_field &f) {
@@ -493,7 +444,7 @@ int upload_peer(ngz_enrich *e, const ngze::PeerMetadata &pm, PeerDev &pd) {
     pd.shape_cols.clear();
     pd.cols.clear();
     if (pm.domain_scoped.size() > NGZ_ENRICH_MAX_DOMAINS)
-        return efail(e, NGZ_E_LIMIT, "a peer with more than 253 observation domains");
+        return ngzs::fail(e, NGZ_E_LIMIT, "a peer with more than 253 observation domains");
     for (const auto &d : pm.domain_scoped) pd.domains.push_back(d.first);
     std::map<ngze::FieldRef, PeerColumn> colmap;
     peer_columns(pm, colmap);
@@ -502,7 +453,7 @@ int upload_peer(ngz_enrich *e, const ngze::PeerMetadata &pm, PeerDev &pd) {
         col_index[c.first] = (uint32_t)pd.cols.size();
         pd.cols.push_back(c.second);
     }
-    if (pd.cols.size() > 0xFFFF) return efail(e, NGZ_E_LIMIT, "a peer with more than 65535 distinct added fields");
+    if (pd.cols.size() > 0xFFFF) return ngzs::fail(e, NGZ_E_LIMIT, "a peer with more than 65535 distinct added fields");
     // entries in visiting order, by map
     std::vector<EnEntry> entries;
     std::vector<EnField> fields;
@@ -547,11 +498,11 @@ int upload_peer(ngz_enrich *e, const ngze::PeerMetadata &pm, PeerDev &pd) {
         }
         return NGZ_OK;
     };
-    if (scan_map(pm.global, 0)) return efail(e, NGZ_E_LIMIT, "too many scopes in one map");
+    if (scan_map(pm.global, 0)) return ngzs::fail(e, NGZ_E_LIMIT, "too many scopes in one map");
     uint32_t di = 0;
     for (const auto &d : pm.domain_scoped)
-        if (scan_map(d.second, 1 + di++)) return efail(e, NGZ_E_LIMIT, "too many scopes in one map");
-    if (fields.size() >> 31 || entries.size() >> 31) return efail(e, NGZ_E_LIMIT, "peer cache too large");
+        if (scan_map(d.second, 1 + di++)) return ngzs::fail(e, NGZ_E_LIMIT, "too many scopes in one map");
+    if (fields.size() >> 31 || entries.size() >> 31) return ngzs::fail(e, NGZ_E_LIMIT, "peer cache too large");
     // one open-addressing table per shape
     const size_t NSH = pd.shapes.size();
     std::vector<uint64_t> count(NSH, 0);
@@ -562,7 +513,7 @@ int upload_peer(ngz_enrich *e, const ngze::PeerMetadata &pm, PeerDev &pd) {
     for (size_t s = 0; s < NSH; ++s) {
         uint32_t bits = e->table_bits ? (uint32_t)e->table_bits : 3;
         while (bits < 31 && (1ull << bits) < (e->table_bits ? count[s] + 1 : 2 * count[s] + 1)) ++bits;
-        if (bits >= 31) return efail(e, NGZ_E_LIMIT, "peer cache too large");
+        if (bits >= 31) return ngzs::fail(e, NGZ_E_LIMIT, "peer cache too large");
         pd.shape_bits[s] = bits;
         pd.shape_slot0[s] = total_slots;
         total_slots += 1ull << bits;
@@ -578,32 +529,19 @@ int upload_peer(ngz_enrich *e, const ngze::PeerMetadata &pm, PeerDev &pd) {
     }
     if (pd.d_entries.ensure(entries.size() + 1) || pd.d_fields.ensure(fields.size() + 1) ||
         pd.d_slots.ensure(total_slots + 1) || pd.d_domains.ensure(pd.domains.size() + 1))
-        return efail(e, NGZ_E_NOMEM, "enrichment tables");
-    if (!entries.empty()) EN_HIP(e, hipMemcpy(pd.d_entries.p, entries.data(), entries.size() * sizeof(EnEntry), hipMemcpyHostToDevice));
-    if (!fields.empty()) EN_HIP(e, hipMemcpy(pd.d_fields.p, fields.data(), fields.size() * sizeof(EnField), hipMemcpyHostToDevice));
-    if (total_slots) EN_HIP(e, hipMemcpy(pd.d_slots.p, slots.data(), total_slots * sizeof(uint32_t), hipMemcpyHostToDevice));
+        return ngzs::fail(e, NGZ_E_NOMEM, "enrichment tables");
+    if (!entries.empty()) NGZ_STAGE_HIP(e, hipMemcpy(pd.d_entries.p, entries.data(), entries.size() * sizeof(EnEntry), hipMemcpyHostToDevice));
+    if (!fields.empty()) NGZ_STAGE_HIP(e, hipMemcpy(pd.d_fields.p, fields.data(), fields.size() * sizeof(EnField), hipMemcpyHostToDevice));
+    if (total_slots) NGZ_STAGE_HIP(e, hipMemcpy(pd.d_slots.p, slots.data(), total_slots * sizeof(uint32_t), hipMemcpyHostToDevice));
     if (!pd.domains.empty())
-        EN_HIP(e, hipMemcpy(pd.d_domains.p, pd.domains.data(), pd.domains.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        NGZ_STAGE_HIP(e, hipMemcpy(pd.d_domains.p, pd.domains.data(), pd.domains.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     if (e->h_arena.size() > e->arena_uploaded) {
-        if (e->d_arena.ensure(e->h_arena.size() + 1)) return efail(e, NGZ_E_NOMEM, "value arena");
-        EN_HIP(e, hipMemcpy(e->d_arena.p, e->h_arena.data(), e->h_arena.size(), hipMemcpyHostToDevice));
+        if (e->d_arena.ensure(e->h_arena.size() + 1)) return ngzs::fail(e, NGZ_E_NOMEM, "value arena");
+        NGZ_STAGE_HIP(e, hipMemcpy(e->d_arena.p, e->h_arena.data(), e->h_arena.size(), hipMemcpyHostToDevice));
         e->arena_uploaded = e->h_arena.size();
     }
     pd.generation = pm.generation;
     pd.table_bits = e->table_bits;
-    return NGZ_OK;
-}
-
-int device_init(ngz_enrich *e) {
-    if (e->device_ready) return NGZ_OK;
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || e->device < 0 || e->device >= n) return efail(e, NGZ_E_DEVICE, "no such device");
-    EN_HIP(e, hipSetDevice(e->device));
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, e->device) == hipSuccess && prop.multiProcessorCount > 0) e->n_cus = prop.multiProcessorCount;
-    EN_HIP(e, hipEventCreate(&e->ev[0]));
-    EN_HIP(e, hipEventCreate(&e->ev[1]));
-    e->device_ready = true;
     return NGZ_OK;
 }
 
@@ -646,10 +584,6 @@ void ngz_enrich_destroy(ngz_enrich *e) {
         }
         e->d_meta.release();
         e->d_counters.release();
-        if (e->h_meta) hipHostFree(e->h_meta);
-        if (e->h_counters) hipHostFree(e->h_counters);
-        for (hipEvent_t ev : e->ev)
-            if (ev) hipEventDestroy(ev);
     }
     delete e;
 }
@@ -663,7 +597,7 @@ int ngz_enrich_set_option(ngz_enrich *e, int opt, int64_t value) {
         e->table_bits = value;
         return NGZ_OK;
     }
-    return efail(e, NGZ_E_INVALID, "option");
+    return ngzs::fail(e, NGZ_E_INVALID, "option");
 }
 
 int ngz_enrich_op(ngz_enrich *e, const ngz_enrich_operation *op) {
@@ -671,10 +605,10 @@ int ngz_enrich_op(ngz_enrich *e, const ngz_enrich_operation *op) {
     if (op->n_scope && op->scope && op->n_scope <= NGZ_ENRICH_MAX_SCOPE_FIELDS)
         for (uint32_t i = 0; i < op->n_scope; ++i)
             if (!scope_ie_ok(op->scope[i]))
-                return efail(e, NGZ_E_LIMIT, "a scope field of a float, string, octet, list or unknown IE");
+                return ngzs::fail(e, NGZ_E_LIMIT, "a scope field of a float, string, octet, list or unknown IE");
     std::string why;
     const int rc = e->cache.apply(*op, &why);
-    if (rc) return efail(e, rc, why);
+    if (rc) return ngzs::fail(e, rc, why);
     return NGZ_OK;
 }
 
@@ -685,9 +619,9 @@ int ngz_enrich_lookup(ngz_enrich *e, const ngz_enrich_peer *peer, uint32_t obs_d
                       uint32_t n_record, ngz_enrich_resolved *out, uint32_t cap) {
     if (!e || !peer || (n_record && !record) || (cap && !out)) return NGZ_E_INVALID;
     ngze::PeerIp ip;
-    if (!ngze::peer_ip(peer, &ip)) return efail(e, NGZ_E_INVALID, "peer address family");
+    if (!ngze::peer_ip(peer, &ip)) return ngzs::fail(e, NGZ_E_INVALID, "peer address family");
     for (uint32_t i = 0; i < n_record; ++i)
-        if (record[i].len && !record[i].value) return efail(e, NGZ_E_INVALID, "record field without a value");
+        if (record[i].len && !record[i].value) return ngzs::fail(e, NGZ_E_INVALID, "record field without a value");
     const std::vector<ngze::Resolved> r = e->cache.lookup(ip, obs_domain_id, record, n_record);
     for (size_t i = 0; i < r.size() && i < cap; ++i) {
         ngz_enrich_resolved &o = out[i];
@@ -708,13 +642,12 @@ int ngz_enrich_apply(ngz_enrich *e, ngz_ctx *ctx, const ngz_batch_out *out, cons
     if (!e || !ctx || !out || !peer) return NGZ_E_INVALID;
     if (batch_stats) memset(batch_stats, 0, sizeof *batch_stats);
     ngze::PeerIp ip;
-    if (!ngze::peer_ip(peer, &ip)) return efail(e, NGZ_E_INVALID, "peer address family");
-    if (ctx->device != e->device) return efail(e, NGZ_E_INVALID, "the context is on another device");
-    if (ctx->async.pending.load()) return efail(e, NGZ_E_INVALID, "a submitted decode is pending on the context");
+    if (!ngze::peer_ip(peer, &ip)) return ngzs::fail(e, NGZ_E_INVALID, "peer address family");
+    if (int rc = ngzs::check_ctx(e, ctx)) return rc;
     const uint32_t S = out->n_slots, D = out->n_dgrams, NS = out->n_sets;
-    if (S > NGZ_MAX_SLOTS || (S && !out->slots)) return efail(e, NGZ_E_INVALID, "slot table");
-    if (int rc = device_init(e)) return rc;
-    EN_HIP(e, hipSetDevice(e->device));
+    if (!ngzs::slot_table_ok(out)) return ngzs::fail(e, NGZ_E_INVALID, "slot table");
+    if (int rc = ngzs::device_init(e)) return rc;
+    NGZ_STAGE_HIP(e, hipSetDevice(e->device));
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
     // the results of an earlier apply for this context are void from here on
     std::unique_ptr<ngz_enrich::CtxResult> &cslot = e->by_ctx[ctx];
@@ -775,10 +708,8 @@ int ngz_enrich_apply(ngz_enrich *e, ngz_ctx *ctx, const ngz_batch_out *out, cons
         rowdom_bytes += ((uint64_t)si.n_records + 15) & ~15ull;  // 16-byte aligned, room for a last quad
         w.mask_off = take(rows4 * 4);
         if (!si.n_records) continue;
-        const int nf = ngz_slot_fields(ctx, s, nullptr, 0);
-        if (nf < 0) return efail(e, NGZ_E_INVALID, "ngz_slot_fields: not the context's last batch");
-        fi.resize(std::max(nf, 1));
-        ngz_slot_fields(ctx, s, fi.data(), (uint32_t)nf);
+        const int nf = ngzs::slot_fields(e, ctx, s, fi);
+        if (nf < 0) return nf;
         // FieldRef -> field of the template's non-scope fields (occurrence index per IE, cache.rs:452-453)
         std::map<ngze::FieldRef, int> by_ref;
         std::map<std::pair<uint32_t, uint16_t>, uint16_t> seen;
@@ -802,7 +733,7 @@ int ngz_enrich_apply(ngz_enrich *e, ngz_ctx *ctx, const ngz_batch_out *out, cons
                 if (candidate) field_of[f] = it->second;
             }
             if (!candidate) continue;
-            if (w.k.n_shapes == NGZ_ENRICH_MAX_SHAPES) return efail(e, NGZ_E_LIMIT, "a slot plan with more than 8 scope shapes");
+            if (w.k.n_shapes == NGZ_ENRICH_MAX_SHAPES) return ngzs::fail(e, NGZ_E_LIMIT, "a slot plan with more than 8 scope shapes");
             EnShape &ks = w.k.shape[w.k.n_shapes++];
             ks.slots = pd->d_slots.p + pd->shape_slot0[sh];
             ks.bits = pd->shape_bits[sh];
@@ -814,9 +745,9 @@ int ngz_enrich_apply(ngz_enrich *e, ngz_ctx *ctx, const ngz_batch_out *out, cons
             pcols.insert(pd->shape_cols[sh].begin(), pd->shape_cols[sh].end());
         }
         if (!w.k.n_shapes) continue;
-        if (pcols.size() > NGZ_ENRICH_MAX_COLUMNS) return efail(e, NGZ_E_LIMIT, "a slot plan with more than 32 added columns");
+        if (pcols.size() > NGZ_ENRICH_MAX_COLUMNS) return ngzs::fail(e, NGZ_E_LIMIT, "a slot plan with more than 32 added columns");
         if (!si.columns || ((uintptr_t)si.columns & 15) || (si.capacity & 3) || si.capacity < si.n_records)
-            return efail(e, NGZ_E_LIMIT, "unexpected column block alignment");
+            return ngzs::fail(e, NGZ_E_LIMIT, "unexpected column block alignment");
         w.launches = true;
         for (uint32_t pc : pcols) {  // ascending peer column = ascending FieldRef
             const PeerColumn &c = pd->cols[pc];
@@ -838,22 +769,21 @@ int ngz_enrich_apply(ngz_enrich *e, ngz_ctx *ctx, const ngz_batch_out *out, cons
         w.k.entries = pd->d_entries.p;
         w.k.fields = pd->d_fields.p;
     }
-    if (rowdom_bytes >> 40 || out_bytes >> 44) return efail(e, NGZ_E_LIMIT, "batch too large");
+    if (rowdom_bytes >> 40 || out_bytes >> 44) return ngzs::fail(e, NGZ_E_LIMIT, "batch too large");
     const size_t n_counters = EN_STATS + 1 + S;
     const size_t n_meta = 2ull * S + 2;
     if (cr.d_out.ensure(out_bytes + 256) || cr.d_rowdom.ensure(rowdom_bytes + 16) || e->d_meta.ensure(n_meta) ||
-        e->d_counters.ensure(n_counters) || pinned_reserve(&e->h_meta, &e->h_meta_cap, n_meta) ||
-        pinned_reserve(&e->h_counters, &e->h_counters_cap, n_counters))
-        return efail(e, NGZ_E_NOMEM, "enricher buffers");
-    uint32_t *h_rows = (uint32_t *)(e->h_meta + S);
+        e->d_counters.ensure(n_counters) || e->h_meta.reserve(n_meta) || e->h_counters.reserve(n_counters))
+        return ngzs::fail(e, NGZ_E_NOMEM, "enricher buffers");
+    uint32_t *h_rows = (uint32_t *)(e->h_meta.p + S);
     for (uint32_t s = 0; s < S; ++s) {
-        e->h_meta[s] = row_off[s];
+        e->h_meta.p[s] = row_off[s];
         h_rows[s] = slot_rows[s];
     }
-    EN_HIP(e, hipEventRecord(e->ev[0], st));
-    if (S) EN_HIP(e, hipMemcpyAsync(e->d_meta.p, e->h_meta, n_meta * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-    EN_HIP(e, hipMemsetAsync(e->d_counters.p, 0, n_counters * sizeof(unsigned long long), st));
-    EN_HIP(e, hipMemsetAsync(cr.d_rowdom.p, 0, rowdom_bytes + 16, st));
+    NGZ_STAGE_HIP(e, hipEventRecord(e->ev[0], st));
+    if (S) NGZ_STAGE_HIP(e, hipMemcpyAsync(e->d_meta.p, e->h_meta.p, n_meta * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    NGZ_STAGE_HIP(e, hipMemsetAsync(e->d_counters.p, 0, n_counters * sizeof(unsigned long long), st));
+    NGZ_STAGE_HIP(e, hipMemsetAsync(cr.d_rowdom.p, 0, rowdom_bytes + 16, st));
     unsigned long long *d_stats = e->d_counters.p, *d_bad = e->d_counters.p + EN_STATS + 1;
     unsigned int *d_err = (unsigned int *)(e->d_counters.p + EN_STATS);
     if (NS && D && S) {
@@ -861,7 +791,7 @@ int ngz_enrich_apply(ngz_enrich *e, ngz_ctx *ctx, const ngz_batch_out *out, cons
         hipLaunchKernelGGL(k_enrich_sets, dim3(nb), dim3(256), 0, st, out->sets, NS, out->dgrams, D, S,
                            (const uint32_t *)(e->d_meta.p + S), (const uint64_t *)e->d_meta.p, cr.d_rowdom.p,
                            pd ? (const uint32_t *)pd->d_domains.p : nullptr, pd ? (uint32_t)pd->domains.size() : 0u, d_bad, d_err);
-        EN_HIP(e, hipGetLastError());
+        NGZ_STAGE_HIP(e, hipGetLastError());
     }
     uint32_t launches = 0;
     for (uint32_t s = 0; s < S; ++s) {
@@ -870,7 +800,7 @@ int ngz_enrich_apply(ngz_enrich *e, ngz_ctx *ctx, const ngz_batch_out *out, cons
         uint32_t *mask = (uint32_t *)(cr.d_out.p + w.mask_off);
         results[s].mask = mask;
         if (!w.launches) {  // its masks read 0
-            EN_HIP(e, hipMemsetAsync(mask, 0, (((uint64_t)slot_rows[s] + 3) & ~3ull) * 4, st));
+            NGZ_STAGE_HIP(e, hipMemsetAsync(mask, 0, (((uint64_t)slot_rows[s] + 3) & ~3ull) * 4, st));
             continue;
         }
         for (uint32_t c = 0; c < w.k.n_cols; ++c) {
@@ -883,21 +813,21 @@ int ngz_enrich_apply(ngz_enrich *e, ngz_ctx *ctx, const ngz_batch_out *out, cons
         const uint64_t quads = ((uint64_t)slot_rows[s] + EN_ROWS_PER_LANE - 1) / EN_ROWS_PER_LANE;
         const uint32_t nb = (uint32_t)std::min<uint64_t>((quads + EN_THREADS - 1) / EN_THREADS, (uint64_t)e->n_cus * 16);
         hipLaunchKernelGGL(k_enrich, dim3(nb), dim3(EN_THREADS), 0, st, w.k);
-        EN_HIP(e, hipGetLastError());
+        NGZ_STAGE_HIP(e, hipGetLastError());
         ++launches;
     }
-    EN_HIP(e, hipEventRecord(e->ev[1], st));
-    EN_HIP(e, hipMemcpyAsync(e->h_counters, e->d_counters.p, n_counters * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    EN_HIP(e, hipStreamSynchronize(st));
-    EN_HIP(e, hipEventElapsedTime(&e->apply_ms, e->ev[0], e->ev[1]));
-    if (e->h_counters[EN_STATS] & 1)
-        return efail(e, NGZ_E_INVALID, "a data set outside the batch's tables: `out` is not the context's last decode");
+    NGZ_STAGE_HIP(e, hipEventRecord(e->ev[1], st));
+    NGZ_STAGE_HIP(e, hipMemcpyAsync(e->h_counters.p, e->d_counters.p, n_counters * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    NGZ_STAGE_HIP(e, hipStreamSynchronize(st));
+    NGZ_STAGE_HIP(e, hipEventElapsedTime(&e->apply_ms, e->ev[0], e->ev[1]));
+    const unsigned long long *hc = e->h_counters.p;
+    if (hc[EN_STATS] & 1) return ngzs::fail_sets(e);
     ngz_enrich_stats bs{};
-    bs.records_matched = e->h_counters[0];
-    bs.fields_added = e->h_counters[1];
+    bs.records_matched = hc[0];
+    bs.fields_added = hc[1];
     for (uint32_t s = 0; s < S; ++s) {
         if (!slot_rows[s]) continue;
-        const uint64_t ok_rows = slot_rows[s] - std::min<uint64_t>(slot_rows[s], e->h_counters[EN_STATS + 1 + s]);
+        const uint64_t ok_rows = ngzs::ok_rows(slot_rows[s], hc[EN_STATS + 1 + s]);
         if (results[s].dropped) bs.records_dropped += ok_rows;
         else bs.records_processed += ok_rows;
     }
@@ -926,8 +856,8 @@ int ngz_enrich_slot_columns(ngz_enrich *e, ngz_ctx *ctx, uint32_t slot, ngz_enri
                             const uint32_t **dev_mask, uint32_t *n) {
     if (!e || !ctx || (cap && !cols)) return NGZ_E_INVALID;
     const std::vector<ngze::SlotResult> *res = ngze::results_for(e, ctx);
-    if (!res) return efail(e, NGZ_E_INVALID, "the context's last batch is not the batch last applied on it");
-    if (slot >= res->size()) return efail(e, NGZ_E_INVALID, "no such slot in the batch last applied");
+    if (!res) return ngzs::fail(e, NGZ_E_INVALID, "the context's last batch is not the batch last applied on it");
+    if (slot >= res->size()) return ngzs::fail(e, NGZ_E_INVALID, "no such slot in the batch last applied");
     const ngze::SlotResult &r = (*res)[slot];
     for (size_t i = 0; i < r.cols.size() && i < cap; ++i) cols[i] = r.cols[i];
     if (dev_mask) *dev_mask = r.mask;
@@ -937,19 +867,19 @@ int ngz_enrich_slot_columns(ngz_enrich *e, ngz_ctx *ctx, uint32_t slot, ngz_enri
 
 int ngz_enrich_row_fields(ngz_enrich *e, ngz_ctx *ctx, uint32_t slot, uint32_t row, ngz_field_value *out, uint32_t cap) {
     if (!e || !ctx || (cap && !out)) return NGZ_E_INVALID;
-    if (!ngze::results_for(e, ctx)) return efail(e, NGZ_E_INVALID, "the context's last batch is not the batch last applied on it");
+    if (!ngze::results_for(e, ctx)) return ngzs::fail(e, NGZ_E_INVALID, "the context's last batch is not the batch last applied on it");
     ngz_enrich::CtxResult &cr = *e->by_ctx[ctx];
-    if (slot >= cr.results.size() || row >= cr.results[slot].rows) return efail(e, NGZ_E_INVALID, "no such row");
+    if (slot >= cr.results.size() || row >= cr.results[slot].rows) return ngzs::fail(e, NGZ_E_INVALID, "no such row");
     if (cr.h_out.empty()) {  // one D2H of the masks, the added columns and the row bytes
-        EN_HIP(e, hipSetDevice(e->device));
+        NGZ_STAGE_HIP(e, hipSetDevice(e->device));
         cr.h_out.resize(cr.out_bytes + 1);
         cr.h_rowdom.resize(cr.rowdom_bytes + 1);
-        if (cr.out_bytes) EN_HIP(e, hipMemcpy(cr.h_out.data(), cr.d_out.p, cr.out_bytes, hipMemcpyDeviceToHost));
-        if (cr.rowdom_bytes) EN_HIP(e, hipMemcpy(cr.h_rowdom.data(), cr.d_rowdom.p, cr.rowdom_bytes, hipMemcpyDeviceToHost));
+        if (cr.out_bytes) NGZ_STAGE_HIP(e, hipMemcpy(cr.h_out.data(), cr.d_out.p, cr.out_bytes, hipMemcpyDeviceToHost));
+        if (cr.rowdom_bytes) NGZ_STAGE_HIP(e, hipMemcpy(cr.h_rowdom.data(), cr.d_rowdom.p, cr.rowdom_bytes, hipMemcpyDeviceToHost));
     }
     const ngze::SlotResult &r = cr.results[slot];
     // a record the reference never enriches: one with scope fields, or of a message that did not decode
-    if (r.dropped || !cr.h_rowdom[cr.row_off[slot] + row]) return efail(e, NGZ_E_INVALID, "the row is not an enriched record");
+    if (r.dropped || !cr.h_rowdom[cr.row_off[slot] + row]) return ngzs::fail(e, NGZ_E_INVALID, "the row is not an enriched record");
     uint32_t mask;
     memcpy(&mask, cr.h_out.data() + ((const uint8_t *)r.mask - cr.d_out.p) + 4ull * row, 4);
     uint32_t n = 0;
@@ -1021,24 +951,24 @@ int64_t ngz_enrich_batch_json(ngz_enrich *e, ngz_renorm *renorm, ngz_ctx *ctx, c
                               void *user) {
     if (!e || !ctx || !fn) return NGZ_E_INVALID;
     if (!ngze::results_for(e, ctx) || ctx->async.pending.load())
-        return efail(e, NGZ_E_INVALID, "the context's last batch is not the batch last applied on it");
+        return ngzs::fail(e, NGZ_E_INVALID, "the context's last batch is not the batch last applied on it");
     ngz_enrich::CtxResult &cr = *e->by_ctx[ctx];
     const size_t S = cr.results.size();
-    if (S != ctx->slot_infos.size()) return efail(e, NGZ_E_INVALID, "slot table");
-    EN_HIP(e, hipSetDevice(e->device));
+    if (S != ctx->slot_infos.size()) return ngzs::fail(e, NGZ_E_INVALID, "slot table");
+    NGZ_STAGE_HIP(e, hipSetDevice(e->device));
     if (cr.h_out.empty()) {
         cr.h_out.resize(cr.out_bytes + 1);
         cr.h_rowdom.resize(cr.rowdom_bytes + 1);
-        if (cr.out_bytes) EN_HIP(e, hipMemcpy(cr.h_out.data(), cr.d_out.p, cr.out_bytes, hipMemcpyDeviceToHost));
-        if (cr.rowdom_bytes) EN_HIP(e, hipMemcpy(cr.h_rowdom.data(), cr.d_rowdom.p, cr.rowdom_bytes, hipMemcpyDeviceToHost));
+        if (cr.out_bytes) NGZ_STAGE_HIP(e, hipMemcpy(cr.h_out.data(), cr.d_out.p, cr.out_bytes, hipMemcpyDeviceToHost));
+        if (cr.rowdom_bytes) NGZ_STAGE_HIP(e, hipMemcpy(cr.h_rowdom.data(), cr.d_rowdom.p, cr.rowdom_bytes, hipMemcpyDeviceToHost));
     }
     ngzh::RenormJson mode;
     std::vector<uint8_t> flags;
     mode.slot_flags.assign(S, nullptr);
     if (renorm) {
         if (const int rc = ngzh::renorm_flags_host(renorm, ctx, flags, mode.slot_flags))
-            return efail(e, rc, "the renormalizer has not applied the context's last batch");
-        if (mode.slot_flags.size() != S) return efail(e, NGZ_E_INVALID, "slot table");
+            return ngzs::fail(e, rc, "the renormalizer has not applied the context's last batch");
+        if (mode.slot_flags.size() != S) return ngzs::fail(e, NGZ_E_INVALID, "slot table");
     }
     mode.enrich.resize(S);
     for (size_t s = 0; s < S; ++s) {
@@ -1059,7 +989,7 @@ int64_t ngz_enrich_batch_json(ngz_enrich *e, ngz_renorm *renorm, ngz_ctx *ctx, c
     }
     ngzh::JsonView v;
     const int rc = ngzh::json_view_load(ctx, host_bytes, v);
-    if (rc) return efail(e, rc, "json_view_load");
+    if (rc) return ngzs::fail(e, rc, "json_view_load");
     int64_t lines = 0;
     std::string s;
     for (uint32_t d = 0; d < ctx->last_in.n; ++d) {
@@ -1112,58 +1042,24 @@ int ngz_enrich_template_plan(ngz_enrich *e, const ngz_enrich_peer *peer, const u
     if (!e || !peer || !tmpl || !out) return NGZ_E_INVALID;
     memset(out, 0, sizeof *out);
     ngze::PeerIp ip;
-    if (!ngze::peer_ip(peer, &ip)) return efail(e, NGZ_E_INVALID, "peer address family");
+    if (!ngze::peer_ip(peer, &ip)) return ngzs::fail(e, NGZ_E_INVALID, "peer address family");
     const bool options = (proto & NGZ_ENRICH_OPTIONS) != 0;
     proto &= ~NGZ_ENRICH_OPTIONS;
-    if (proto != 10 && proto != 9) return efail(e, NGZ_E_INVALID, "protocol");
-    // the template record's specifiers, as ngz_renorm_template_plan reads them
-    size_t pos = 2;
-    uint32_t n_fields = 0, n_scope = 0, seen_fields = 0;
-    size_t scope_end = 0, end = len;
-    if (!options) {
-        if (len < 4) return efail(e, NGZ_E_INVALID, "template record");
-        n_fields = ngzh::rd16(tmpl + 2);
-        pos = 4;
-    } else {
-        if (len < 6) return efail(e, NGZ_E_INVALID, "template record");
-        pos = 6;
-        if (proto == 10) {
-            n_fields = ngzh::rd16(tmpl + 2);
-            n_scope = ngzh::rd16(tmpl + 4);
-            if (n_scope > n_fields) return efail(e, NGZ_E_INVALID, "template record");
-        } else {
-            scope_end = pos + ngzh::rd16(tmpl + 2);
-            end = scope_end + ngzh::rd16(tmpl + 4);
-            if (end > len) return efail(e, NGZ_E_INVALID, "template record");
-        }
-    }
-    const bool by_bytes = options && proto == 9;
+    if (proto != 10 && proto != 9) return ngzs::fail(e, NGZ_E_INVALID, "protocol");
     std::map<ngze::FieldRef, std::pair<uint8_t, uint16_t>> by_ref;  // non-scope FieldRef -> column kind, width
     std::map<std::pair<uint32_t, uint16_t>, uint16_t> seen;
-    while (by_bytes ? pos < end : seen_fields < n_fields) {
-        if (pos + 4 > len) return efail(e, NGZ_E_INVALID, "template record");
-        uint32_t code = ngzh::rd16(tmpl + pos);
-        const uint32_t L = ngzh::rd16(tmpl + pos + 2);
-        pos += 4;
-        const bool scope = by_bytes ? pos - 4 < scope_end : seen_fields < n_scope;
-        uint32_t pen = 0;
-        if (!(by_bytes && scope) && (code & 0x8000)) {
-            if (pos + 4 > len) return efail(e, NGZ_E_INVALID, "template record");
-            pen = ngzh::rd32(tmpl + pos);
-            pos += 4;
-            code &= 0x7FFF;
-        }
-        if (++seen_fields > 0x7FFF) return efail(e, NGZ_E_INVALID, "template record");
-        if (scope) { out->dropped = 1; continue; }
+    const int rc = ngzt::walk_template_record(tmpl, len, proto, options, [&](const ngzt::FieldSpec &f) {
+        if (f.scope) { out->dropped = 1; return; }
         ngze::FieldRef r;
-        r.pen = pen;
-        r.ie = (uint16_t)code;
-        r.index = seen[{pen, (uint16_t)code}]++;
+        r.pen = f.pen;
+        r.ie = f.ie;
+        r.index = seen[{f.pen, f.ie}]++;
         uint8_t kind;
         uint16_t width;
-        plan_rule(pen, (uint16_t)code, L, &kind, &width);
+        plan_rule(f.pen, f.ie, f.length, &kind, &width);
         by_ref[r] = {kind, width};
-    }
+    });
+    if (rc) return ngzs::fail(e, rc, "template record");
     const ngze::PeerMetadata *pm = e->cache.peer(ip);
     if (out->dropped || !pm) return NGZ_OK;
     std::map<ngze::FieldRef, PeerColumn> colmap;
@@ -1189,8 +1085,8 @@ int ngz_enrich_template_plan(ngz_enrich *e, const ngz_enrich_peer *peer, const u
         cand.push_back(&sh.first);
         cols.insert(sh.second.begin(), sh.second.end());
     }
-    if (cand.size() > NGZ_ENRICH_MAX_SHAPES) return efail(e, NGZ_E_LIMIT, "a slot plan with more than 8 scope shapes");
-    if (cols.size() > NGZ_ENRICH_MAX_COLUMNS) return efail(e, NGZ_E_LIMIT, "a slot plan with more than 32 added columns");
+    if (cand.size() > NGZ_ENRICH_MAX_SHAPES) return ngzs::fail(e, NGZ_E_LIMIT, "a slot plan with more than 8 scope shapes");
+    if (cols.size() > NGZ_ENRICH_MAX_COLUMNS) return ngzs::fail(e, NGZ_E_LIMIT, "a slot plan with more than 32 added columns");
     out->n_shapes = (uint8_t)cand.size();
     for (size_t s = 0; s < cand.size(); ++s) {
         out->shape_len[s] = (uint8_t)cand[s]->size();

@@ -15,6 +15,7 @@
 #include "ngz/flow_options.h"
 #include "ngz_host.h"
 #include "ngz_options_plan.h"
+#include "ngz_stage.h"
 
 namespace {
 
@@ -25,7 +26,7 @@ constexpr uint64_t SLOT_NOT_OPTIONS = ~0ull;      // slot_off: a slot without sc
 constexpr uint64_t SLOT_COUNT_ONLY = ~0ull - 1;   // an options slot whose live rows are only counted
 // device counters
 constexpr uint32_t C_OK_DGRAMS = 0, C_OPS = 1, C_ID_ERRORS = 2, C_ERR = 3, C_SLOT0 = 4;
-constexpr uint32_t ERR_SETS = 1, ERR_VLEN = 2;
+constexpr uint32_t ERR_SETS = 1, ERR_VLEN = 2;  // ERR_SETS: the bit ngzs::for_each_set sets
 
 enum : uint32_t { V_FIXED = 0, V_STR = 1, V_VLEN = 2 };
 struct OpValue {
@@ -55,27 +56,6 @@ struct OpPlan {
     unsigned long long bytes_size;
     unsigned long long *counters;
 };
-
-__device__ __forceinline__ uint64_t op_wave_sum(uint64_t v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-
-// Block-wide add of per-lane counts: a wave reduction, one LDS atomic per wave, one global atomic
-// per block and counter.  Every thread of the block calls it.
-template <int N>
-__device__ __forceinline__ void op_block_add(unsigned long long *acc, const uint64_t (&v)[N], unsigned long long *const (&dst)[N]) {
-    if (threadIdx.x < N) acc[threadIdx.x] = 0;
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        const uint64_t s = op_wave_sum(v[i]);
-        if ((threadIdx.x & 63) == 0 && s) atomicAdd(&acc[i], (unsigned long long)s);
-    }
-    __syncthreads();
-    if (threadIdx.x < N && acc[threadIdx.x]) atomicAdd(dst[threadIdx.x], acc[threadIdx.x]);
-}
 
 // Columns start at capacity * col_off: only their cells' own alignment is known, so cells are read
 // bytewise (this path carries a few bytes per options row)
@@ -110,7 +90,7 @@ __device__ __forceinline__ uint32_t op_value(const OpValue &v, uint32_t row, con
     return len;
 }
 
-// One thread per data set, as k_enrich_sets: the rows of an options slot's set whose message
+// One thread per data set (ngzs::for_each_set): the rows of an options slot's set whose message
 // decoded get the set's index + 1 and count as live rows of the slot; the other rows keep the 0
 // the buffer was cleared to.  Then the batch's NGZ_DG_OK messages are counted.
 __global__ __launch_bounds__(OP_THREADS) void k_options_sets(const ngz_set_info *__restrict__ sets, uint32_t n_sets,
@@ -119,24 +99,19 @@ __global__ __launch_bounds__(OP_THREADS) void k_options_sets(const ngz_set_info 
                                                              uint32_t *__restrict__ rowset, unsigned long long *__restrict__ counters) {
     __shared__ unsigned long long acc[1];
     const uint32_t stride = gridDim.x * blockDim.x, t0 = blockIdx.x * blockDim.x + threadIdx.x;
-    for (uint32_t s = t0; s < n_sets; s += stride) {
-        const ngz_set_info si = sets[s];
-        if (!si.n) continue;
-        if (si.dgram >= n_dgrams || si.slot >= n_slots || (uint64_t)si.rec0 + si.n > slot_rows[si.slot]) {
-            atomicOr((unsigned int *)&counters[C_ERR], ERR_SETS);
-            continue;
-        }
+    ngzs::for_each_set(sets, n_sets, hdr, n_dgrams, n_slots, slot_rows, (unsigned int *)&counters[C_ERR],
+                       [&](uint32_t s, const ngz_set_info &si, const ngz_dgram_hdr &h) {
         const uint64_t off = slot_off[si.slot];
-        if (off == SLOT_NOT_OPTIONS || hdr[si.dgram].status != NGZ_DG_OK) continue;
+        if (off == SLOT_NOT_OPTIONS || h.status != NGZ_DG_OK) return;
         atomicAdd(&counters[C_SLOT0 + si.slot], (unsigned long long)si.n);
-        if (off == SLOT_COUNT_ONLY) continue;
+        if (off == SLOT_COUNT_ONLY) return;
         uint32_t *p = rowset + off + si.rec0;
         for (uint32_t r = 0; r < si.n; ++r) p[r] = s + 1u;
-    }
+    });
     uint64_t ok[1] = {0};
     for (uint32_t d = t0; d < n_dgrams; d += stride) ok[0] += hdr[d].status == NGZ_DG_OK ? 1u : 0u;
     unsigned long long *const dst[1] = {&counters[C_OK_DGRAMS]};
-    op_block_add<1>(acc, ok, dst);
+    ngzs::block_add<1>(acc, ok, dst);
 }
 
 // One thread per row of an options slot: the id test and the bytes of the row's packed operations
@@ -169,7 +144,7 @@ __global__ __launch_bounds__(OP_THREADS) void k_options_rows(const OpPlan P) {
     }
     if (err) atomicOr((unsigned int *)&P.counters[C_ERR], err);
     unsigned long long *const dst[2] = {&P.counters[C_OPS], &P.counters[C_ID_ERRORS]};
-    op_block_add<2>(acc, cnt, dst);
+    ngzs::block_add<2>(acc, cnt, dst);
 }
 
 // One thread per row: the row's operations at its scanned offset.  Per operation: the header words
@@ -224,14 +199,10 @@ struct HostSlotPlan {
 
 }  // namespace
 
-struct ngz_options {
-    int device = 0;
+struct ngz_options : ngzs::Stage {
+    ngz_options() : Stage(4) {}
     uint8_t weight = 0;
-    std::string last_error;
     ngz_options_stats totals{};
-    bool device_ready = false;
-    int n_cus = 256;
-    hipEvent_t ev[4]{};
     float harvest_ms = 0;
     int launches = 0;
     ngzh::DevBuf<uint32_t> d_rowset;
@@ -245,29 +216,6 @@ struct ngz_options {
 };
 
 namespace {
-
-int ofail(ngz_options *o, int rc, const std::string &msg) {
-    if (o) o->last_error = msg;
-    return rc;
-}
-
-#define OP_HIP(o, x)                                                                            \
-    do {                                                                                        \
-        hipError_t e_ = (x);                                                                    \
-        if (e_ != hipSuccess) return ofail(o, NGZ_E_DEVICE, std::string(#x) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
-int device_init(ngz_options *o) {
-    if (o->device_ready) return NGZ_OK;
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || o->device < 0 || o->device >= n) return ofail(o, NGZ_E_DEVICE, "no such device");
-    OP_HIP(o, hipSetDevice(o->device));
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, o->device) == hipSuccess && prop.multiProcessorCount > 0) o->n_cus = prop.multiProcessorCount;
-    for (hipEvent_t &ev : o->ev) OP_HIP(o, hipEventCreate(&ev));
-    o->device_ready = true;
-    return NGZ_OK;
-}
 
 // The canonical kind an operation's value has, and how the kernels read it from its column
 bool value_rule(const ngz_field_info &fi, uint32_t pen, uint16_t ie, uint8_t *kind, uint32_t *mode) {
@@ -332,8 +280,6 @@ void ngz_options_destroy(ngz_options *o) {
         o->d_meta.release();
         o->d_scan_tmp.release();
         o->d_packed.release();
-        for (hipEvent_t ev : o->ev)
-            if (ev) hipEventDestroy(ev);
     }
     delete o;
 }
@@ -344,12 +290,11 @@ int ngz_options_harvest(ngz_options *o, ngz_ctx *ctx, const ngz_batch_out *out, 
                         ngz_options_stats *batch_stats, void *hip_stream) {
     if (!o || !ctx || !out || !peer) return NGZ_E_INVALID;
     if (batch_stats) memset(batch_stats, 0, sizeof *batch_stats);
-    if (peer->family != 4 && peer->family != 6) return ofail(o, NGZ_E_INVALID, "peer address family");
-    if (ctx->device != o->device) return ofail(o, NGZ_E_INVALID, "the context is on another device");
-    if (ctx->async.pending.load()) return ofail(o, NGZ_E_INVALID, "a submitted decode is pending on the context");
+    if (peer->family != 4 && peer->family != 6) return ngzs::fail(o, NGZ_E_INVALID, "peer address family");
+    if (int rc = ngzs::check_ctx(o, ctx)) return rc;
     const uint32_t S = out->n_slots, D = out->n_dgrams, NS = out->n_sets;
-    if (S > NGZ_MAX_SLOTS || (S && !out->slots) || S != ctx->slot_version.size() || D != ctx->last_in.n)
-        return ofail(o, NGZ_E_INVALID, "slot table: `out` is not the context's last decode");
+    if (!ngzs::slot_table_ok(out) || S != ctx->slot_version.size() || D != ctx->last_in.n)
+        return ngzs::fail(o, NGZ_E_INVALID, "slot table: `out` is not the context's last decode");
     o->ops.clear();
     o->op_fields.clear();
     o->h_packed.clear();
@@ -377,10 +322,8 @@ int ngz_options_harvest(ngz_options *o, ngz_ctx *ctx, const ngz_batch_out *out, 
         memset(&w.k, 0, sizeof w.k);
         slot_rows[s] = si.n_records;
         if (!si.n_records) continue;
-        const int nf = ngz_slot_fields(ctx, s, nullptr, 0);
-        if (nf < 0) return ofail(o, NGZ_E_INVALID, "ngz_slot_fields: not the context's last batch");
-        fi.resize(std::max(nf, 1));
-        ngz_slot_fields(ctx, s, fi.data(), (uint32_t)nf);
+        const int nf = ngzs::slot_fields(o, ctx, s, fi);
+        if (nf < 0) return nf;
         pf.resize(nf);
         for (int i = 0; i < nf; ++i) {
             pf[i].pen = fi[i].pen;
@@ -389,13 +332,13 @@ int ngz_options_harvest(ngz_options *o, ngz_ctx *ctx, const ngz_batch_out *out, 
         }
         ngz_options_plan plan;
         if (ngzo::plan_fields(pf, si.proto, &plan))
-            return ofail(o, NGZ_E_LIMIT, "an options template with more than 24 scope fields or fields per operation");
+            return ngzs::fail(o, NGZ_E_LIMIT, "an options template with more than 24 scope fields or fields per operation");
         w.outcome = plan.outcome;
         if (plan.outcome == NGZ_OPTIONS_OUT_NOT_OPTIONS) continue;
         any_options = true;
         slot_off[s] = SLOT_COUNT_ONLY;
         if (plan.outcome != NGZ_OPTIONS_OUT_OPS || !plan.n_ops) continue;
-        if (!si.columns || si.capacity < si.n_records) return ofail(o, NGZ_E_LIMIT, "unexpected column block");
+        if (!si.columns || si.capacity < si.n_records) return ngzs::fail(o, NGZ_E_LIMIT, "unexpected column block");
         auto column = [&](uint32_t f) { return (const uint8_t *)si.columns + (uint64_t)si.capacity * fi[f].col_off; };
         HostSlotPlan &hp = hplan[s];
         hp.n_ops = plan.n_ops;
@@ -408,12 +351,12 @@ int ngz_options_harvest(ngz_options *o, ngz_ctx *ctx, const ngz_batch_out *out, 
                 const bool sc = i < plan.n_scope[op];
                 const ngz_options_ref &ref = sc ? plan.scope[op][i] : plan.fields[op][i - plan.n_scope[op]];
                 const uint32_t src = sc ? plan.scope_src[op][i] : plan.fields_src[op][i - plan.n_scope[op]];
-                if (src >= (uint32_t)nf) return ofail(o, NGZ_E_INVALID, "plan source field");
+                if (src >= (uint32_t)nf) return ngzs::fail(o, NGZ_E_INVALID, "plan source field");
                 HostValue hv{ref.pen, ref.ie_id, 0};
                 OpValue &kv = w.k.v[op][i];
                 // a re-tagged name keeps the string-ness of the IE it was read as
                 if (!value_rule(fi[src], fi[src].pen, fi[src].ie_id, &hv.kind, &kv.mode))
-                    return ofail(o, NGZ_E_LIMIT, "an options field of a kind the harvest cannot carry");
+                    return ngzs::fail(o, NGZ_E_LIMIT, "an options field of a kind the harvest cannot carry");
                 kv.col = column(src);
                 kv.width = fi[src].width;
                 hp.v[op].push_back(hv);
@@ -424,7 +367,7 @@ int ngz_options_harvest(ngz_options *o, ngz_ctx *ctx, const ngz_batch_out *out, 
             for (int d = 0; d < 2; ++d) {
                 const ngz_field_info &f = fi[plan.id_src[d]];
                 if ((f.kind != NGZ_K_UINT && f.kind != NGZ_K_SCOPE32) || f.width < 1 || f.width > 8)
-                    return ofail(o, NGZ_E_LIMIT, "an interface or VRF id that is no unsigned integer");
+                    return ngzs::fail(o, NGZ_E_LIMIT, "an interface or VRF id that is no unsigned integer");
                 w.k.id_col[d] = column(plan.id_src[d]);
                 w.k.id_w[d] = f.width;
             }
@@ -437,49 +380,49 @@ int ngz_options_harvest(ngz_options *o, ngz_ctx *ctx, const ngz_batch_out *out, 
         n_rows += si.n_records;
     }
     ngz_options_stats bs{};
-    if (int rc = device_init(o)) return rc;
-    OP_HIP(o, hipSetDevice(o->device));
+    if (int rc = ngzs::device_init(o)) return rc;
+    NGZ_STAGE_HIP(o, hipSetDevice(o->device));
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
     if (!any_options) {
         // no options row: no kernel.  received_flows still counts the messages that decoded: their
         // headers (32 bytes per datagram) are all that is read
         if (D) {
             std::vector<ngz_dgram_hdr> hdr(D);
-            OP_HIP(o, hipMemcpyAsync(hdr.data(), out->dgrams, (size_t)D * sizeof(ngz_dgram_hdr), hipMemcpyDeviceToHost, st));
-            OP_HIP(o, hipStreamSynchronize(st));
+            NGZ_STAGE_HIP(o, hipMemcpyAsync(hdr.data(), out->dgrams, (size_t)D * sizeof(ngz_dgram_hdr), hipMemcpyDeviceToHost, st));
+            NGZ_STAGE_HIP(o, hipStreamSynchronize(st));
             for (const ngz_dgram_hdr &h : hdr) bs.received_flows += h.status == NGZ_DG_OK;
         }
         add_stats(o->totals, bs);
         if (batch_stats) *batch_stats = bs;
         return NGZ_OK;
     }
-    if (n_rows >> 31) return ofail(o, NGZ_E_LIMIT, "batch too large");
+    if (n_rows >> 31) return ngzs::fail(o, NGZ_E_LIMIT, "batch too large");
 
     const size_t n_counters = C_SLOT0 + S, n_meta = 2ull * S + 2;
     size_t scan_bytes = 0;
     if (hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, (unsigned long long *)nullptr, (unsigned long long *)nullptr,
                                          (int)(n_rows + 1), st) != hipSuccess)
-        return ofail(o, NGZ_E_DEVICE, "scan temp size");
+        return ngzs::fail(o, NGZ_E_DEVICE, "scan temp size");
     if (o->d_rowset.ensure(n_rows + 1) || o->d_size.ensure(n_rows + 1) || o->d_offs.ensure(n_rows + 2) ||
         o->d_counters.ensure(n_counters) || o->d_meta.ensure(n_meta) || o->d_scan_tmp.ensure(scan_bytes + 1))
-        return ofail(o, NGZ_E_NOMEM, "harvester buffers");
+        return ngzs::fail(o, NGZ_E_NOMEM, "harvester buffers");
     std::vector<uint64_t> h_meta(n_meta, 0);
     uint32_t *h_rows = (uint32_t *)(h_meta.data() + S);
     for (uint32_t s = 0; s < S; ++s) {
         h_meta[s] = slot_off[s];
         h_rows[s] = slot_rows[s];
     }
-    OP_HIP(o, hipMemcpyAsync(o->d_meta.p, h_meta.data(), n_meta * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-    OP_HIP(o, hipMemsetAsync(o->d_counters.p, 0, n_counters * sizeof(unsigned long long), st));
-    OP_HIP(o, hipMemsetAsync(o->d_rowset.p, 0, (n_rows + 1) * sizeof(uint32_t), st));
-    OP_HIP(o, hipMemsetAsync(o->d_size.p, 0, (n_rows + 1) * sizeof(unsigned long long), st));
-    OP_HIP(o, hipEventRecord(o->ev[0], st));
+    NGZ_STAGE_HIP(o, hipMemcpyAsync(o->d_meta.p, h_meta.data(), n_meta * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    NGZ_STAGE_HIP(o, hipMemsetAsync(o->d_counters.p, 0, n_counters * sizeof(unsigned long long), st));
+    NGZ_STAGE_HIP(o, hipMemsetAsync(o->d_rowset.p, 0, (n_rows + 1) * sizeof(uint32_t), st));
+    NGZ_STAGE_HIP(o, hipMemsetAsync(o->d_size.p, 0, (n_rows + 1) * sizeof(unsigned long long), st));
+    NGZ_STAGE_HIP(o, hipEventRecord(o->ev[0], st));
     {
         const uint64_t items = std::max<uint64_t>(NS, D);
         const uint32_t nb = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((items + OP_THREADS - 1) / OP_THREADS, (uint64_t)o->n_cus * 8));
         hipLaunchKernelGGL(k_options_sets, dim3(nb), dim3(OP_THREADS), 0, st, out->sets, NS, out->dgrams, D, S,
                            (const uint32_t *)(o->d_meta.p + S), (const uint64_t *)o->d_meta.p, o->d_rowset.p, o->d_counters.p);
-        OP_HIP(o, hipGetLastError());
+        NGZ_STAGE_HIP(o, hipGetLastError());
         ++o->launches;
     }
     auto grid = [&](uint32_t rows) {
@@ -497,26 +440,25 @@ int ngz_options_harvest(ngz_options *o, ngz_ctx *ctx, const ngz_batch_out *out, 
         w.k.bytes_size = ctx->last_in.bytes_size;
         w.k.counters = o->d_counters.p;
         hipLaunchKernelGGL(k_options_rows, dim3(grid(w.k.n_rows)), dim3(OP_THREADS), 0, st, w.k);
-        OP_HIP(o, hipGetLastError());
+        NGZ_STAGE_HIP(o, hipGetLastError());
         ++o->launches;
     }
     if (n_rows) {
-        OP_HIP(o, hipcub::DeviceScan::ExclusiveSum(o->d_scan_tmp.p, scan_bytes, o->d_size.p, o->d_offs.p, (int)(n_rows + 1), st));
+        NGZ_STAGE_HIP(o, hipcub::DeviceScan::ExclusiveSum(o->d_scan_tmp.p, scan_bytes, o->d_size.p, o->d_offs.p, (int)(n_rows + 1), st));
         ++o->launches;
     }
-    OP_HIP(o, hipEventRecord(o->ev[1], st));
+    NGZ_STAGE_HIP(o, hipEventRecord(o->ev[1], st));
     std::vector<unsigned long long> h_counters(n_counters, 0);
     unsigned long long total = 0;
-    OP_HIP(o, hipMemcpyAsync(h_counters.data(), o->d_counters.p, n_counters * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    if (n_rows) OP_HIP(o, hipMemcpyAsync(&total, o->d_offs.p + n_rows, sizeof total, hipMemcpyDeviceToHost, st));
-    OP_HIP(o, hipStreamSynchronize(st));
+    NGZ_STAGE_HIP(o, hipMemcpyAsync(h_counters.data(), o->d_counters.p, n_counters * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    if (n_rows) NGZ_STAGE_HIP(o, hipMemcpyAsync(&total, o->d_offs.p + n_rows, sizeof total, hipMemcpyDeviceToHost, st));
+    NGZ_STAGE_HIP(o, hipStreamSynchronize(st));
     float ms = 0;
-    OP_HIP(o, hipEventElapsedTime(&ms, o->ev[0], o->ev[1]));
+    NGZ_STAGE_HIP(o, hipEventElapsedTime(&ms, o->ev[0], o->ev[1]));
     o->harvest_ms = ms;
-    if (h_counters[C_ERR] & ERR_SETS)
-        return ofail(o, NGZ_E_INVALID, "a data set outside the batch's tables: `out` is not the context's last decode");
-    if (h_counters[C_ERR] & ERR_VLEN) return ofail(o, NGZ_E_INVALID, "a variable-length cell outside the batch input");
-    if (total >> 32) return ofail(o, NGZ_E_LIMIT, "more than 4 GiB of operations in one batch");
+    if (h_counters[C_ERR] & ERR_SETS) return ngzs::fail_sets(o);
+    if (h_counters[C_ERR] & ERR_VLEN) return ngzs::fail(o, NGZ_E_INVALID, "a variable-length cell outside the batch input");
+    if (total >> 32) return ngzs::fail(o, NGZ_E_LIMIT, "more than 4 GiB of operations in one batch");
 
     bs.received_flows = h_counters[C_OK_DGRAMS];
     bs.operations_generated = h_counters[C_OPS];
@@ -530,22 +472,22 @@ int ngz_options_harvest(ngz_options *o, ngz_ctx *ctx, const ngz_batch_out *out, 
     }
 
     if (total) {
-        if (o->d_packed.ensure(total + 4)) return ofail(o, NGZ_E_NOMEM, "packed operations");
+        if (o->d_packed.ensure(total + 4)) return ngzs::fail(o, NGZ_E_NOMEM, "packed operations");
         o->h_packed.resize(total);
-        OP_HIP(o, hipEventRecord(o->ev[2], st));
+        NGZ_STAGE_HIP(o, hipEventRecord(o->ev[2], st));
         for (uint32_t s = 0; s < S; ++s) {
             SlotWork &w = work[s];
             if (!w.packs) continue;
             w.k.packed = o->d_packed.p;
             w.k.total = total;
             hipLaunchKernelGGL(k_options_pack, dim3(grid(w.k.n_rows)), dim3(OP_THREADS), 0, st, w.k);
-            OP_HIP(o, hipGetLastError());
+            NGZ_STAGE_HIP(o, hipGetLastError());
             ++o->launches;
         }
-        OP_HIP(o, hipEventRecord(o->ev[3], st));
-        OP_HIP(o, hipMemcpyAsync(o->h_packed.data(), o->d_packed.p, total, hipMemcpyDeviceToHost, st));
-        OP_HIP(o, hipStreamSynchronize(st));
-        OP_HIP(o, hipEventElapsedTime(&ms, o->ev[2], o->ev[3]));
+        NGZ_STAGE_HIP(o, hipEventRecord(o->ev[3], st));
+        NGZ_STAGE_HIP(o, hipMemcpyAsync(o->h_packed.data(), o->d_packed.p, total, hipMemcpyDeviceToHost, st));
+        NGZ_STAGE_HIP(o, hipStreamSynchronize(st));
+        NGZ_STAGE_HIP(o, hipEventElapsedTime(&ms, o->ev[2], o->ev[3]));
         o->harvest_ms += ms;
 
         // the records of all slots, then stream order: set index, record in the set, operation
@@ -558,17 +500,17 @@ int ngz_options_harvest(ngz_options *o, ngz_ctx *ctx, const ngz_batch_out *out, 
         size_t n_values = 0;
         for (uint64_t at = 0; at < total;) {
             uint32_t head[OP_HEADER_WORDS];
-            if (total - at < sizeof head) return ofail(o, NGZ_E_DEVICE, "packed operations: a truncated record");
+            if (total - at < sizeof head) return ngzs::fail(o, NGZ_E_DEVICE, "packed operations: a truncated record");
             memcpy(head, o->h_packed.data() + at, sizeof head);
             const uint32_t s = head[4] & 0xFFFFu, op = head[4] >> 16;
             if (s >= S || op >= hplan[s].n_ops || head[0] < 4u * (OP_HEADER_WORDS + hplan[s].v[op].size()) || head[0] > total - at ||
                 (head[0] & 3u))
-                return ofail(o, NGZ_E_DEVICE, "packed operations: a malformed record");
+                return ngzs::fail(o, NGZ_E_DEVICE, "packed operations: a malformed record");
             recs.push_back(Rec{((uint64_t)head[1] << 32) | head[2], op, at});
             n_values += hplan[s].v[op].size();
             at += head[0];
         }
-        if (recs.size() != bs.operations_generated) return ofail(o, NGZ_E_DEVICE, "packed operations: count mismatch");
+        if (recs.size() != bs.operations_generated) return ngzs::fail(o, NGZ_E_DEVICE, "packed operations: count mismatch");
         std::sort(recs.begin(), recs.end(), [](const Rec &a, const Rec &b) { return a.ord != b.ord ? a.ord < b.ord : a.op < b.op; });
         o->op_fields.assign(n_values + 1, ngz_enrich_field{});
         o->ops.reserve(recs.size());
@@ -585,7 +527,7 @@ int ngz_options_harvest(ngz_options *o, ngz_ctx *ctx, const ngz_batch_out *out, 
             for (size_t i = 0; i < hv.size(); ++i) {
                 uint32_t len;
                 memcpy(&len, p + 4ull * (OP_HEADER_WORDS + i), 4);
-                if (len > (size_t)(end - val)) return ofail(o, NGZ_E_DEVICE, "packed operations: a value past its record");
+                if (len > (size_t)(end - val)) return ngzs::fail(o, NGZ_E_DEVICE, "packed operations: a value past its record");
                 ngz_enrich_field &f = f0[i];
                 f.pen = hv[i].pen;
                 f.ie_id = hv[i].ie;
@@ -616,7 +558,7 @@ uint64_t ngz_options_op_count(ngz_options *o) { return o ? o->ops.size() : 0; }
 
 int ngz_options_op(ngz_options *o, uint64_t i, ngz_enrich_operation *op) {
     if (!o || !op) return NGZ_E_INVALID;
-    if (i >= o->ops.size()) return ofail(o, NGZ_E_INVALID, "no such operation");
+    if (i >= o->ops.size()) return ngzs::fail(o, NGZ_E_INVALID, "no such operation");
     *op = o->ops[i];
     return NGZ_OK;
 }
@@ -631,7 +573,7 @@ int ngz_options_feed(ngz_options *o, ngz_enrich *enricher, uint64_t *n_applied) 
             ++o->totals.ops_refused;
             continue;
         }
-        if (rc) return ofail(o, rc, std::string("ngz_enrich_op: ") + ngz_enrich_last_error(enricher));
+        if (rc) return ngzs::fail(o, rc, std::string("ngz_enrich_op: ") + ngz_enrich_last_error(enricher));
         ++applied;
         if (n_applied) *n_applied = applied;
     }

@@ -5,6 +5,8 @@
 #include <map>
 #include <utility>
 
+#include "ngz_template_record.h"
+
 namespace ngzo {
 namespace {
 
@@ -149,56 +151,6 @@ int plan_fields(const std::vector<PlanField> &fields, int proto, ngz_options_pla
     return NGZ_OK;
 }
 
-static inline uint32_t be16(const uint8_t *p) { return ((uint32_t)p[0] << 8) | p[1]; }
-static inline uint32_t be32(const uint8_t *p) {
-    return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3];
-}
-
-int parse_template(const uint8_t *tmpl, size_t len, int proto, bool options, std::vector<PlanField> *out) {
-    out->clear();
-    size_t pos;
-    uint32_t n_fields = 0, n_scope = 0, seen = 0;
-    size_t scope_end = 0, end = len;
-    if (!options) {  // template id, field count (ipfix.rs:384-413, netflow.rs:324-353)
-        if (len < 4) return NGZ_E_INVALID;
-        n_fields = be16(tmpl + 2);
-        pos = 4;
-    } else {
-        if (len < 6) return NGZ_E_INVALID;
-        pos = 6;
-        if (proto == 10) {  // template id, field count, scope field count
-            n_fields = be16(tmpl + 2);
-            n_scope = be16(tmpl + 4);
-            if (n_scope > n_fields) return NGZ_E_INVALID;
-        } else {  // template id, scope length, options length, in bytes
-            scope_end = pos + be16(tmpl + 2);
-            end = scope_end + be16(tmpl + 4);
-            if (end > len) return NGZ_E_INVALID;
-        }
-    }
-    const bool by_bytes = options && proto == 9;
-    while (by_bytes ? pos < end : seen < n_fields) {
-        if (pos + 4 > len) return NGZ_E_INVALID;
-        uint32_t code = be16(tmpl + pos);
-        pos += 4;
-        const bool scope = by_bytes ? pos - 4 < scope_end : seen < n_scope;
-        uint32_t pen = 0;
-        if (!(by_bytes && scope) && (code & 0x8000)) {
-            if (pos + 4 > len) return NGZ_E_INVALID;
-            pen = be32(tmpl + pos);
-            pos += 4;
-            code &= 0x7FFF;
-        }
-        if (++seen > 0x7FFF) return NGZ_E_INVALID;
-        PlanField f;
-        f.pen = pen;
-        f.ie = (uint16_t)code;
-        f.scope = scope;
-        out->push_back(f);
-    }
-    return NGZ_OK;
-}
-
 }  // namespace ngzo
 
 extern "C" int ngz_options_template_plan(const uint8_t *tmpl, size_t len, int proto, ngz_options_plan *out) {
@@ -208,6 +160,13 @@ extern "C" int ngz_options_template_plan(const uint8_t *tmpl, size_t len, int pr
     proto &= ~NGZ_OPTIONS_OPTIONS;
     if (proto != 10 && proto != 9) return NGZ_E_INVALID;
     std::vector<ngzo::PlanField> fields;
-    if (int rc = ngzo::parse_template(tmpl, len, proto, options, &fields)) return rc;
+    const int rc = ngzt::walk_template_record(tmpl, len, proto, options, [&](const ngzt::FieldSpec &f) {
+        ngzo::PlanField pf;
+        pf.pen = f.pen;
+        pf.ie = f.ie;
+        pf.scope = f.scope;
+        fields.push_back(pf);
+    });
+    if (rc) return rc;
     return ngzo::plan_fields(fields, proto, out);
 }

@@ -20,8 +20,4 @@ struct PlanField {  // one field specifier of a template, scope fields first
 // The plan of a template's records; proto 10 or 9.  NGZ_OK, or NGZ_E_LIMIT past NGZ_OPTIONS_MAX_REFS
 int plan_fields(const std::vector<PlanField> &fields, int proto, ngz_options_plan *out);
 
-// The field specifiers of one (options) template record, in the layouts ngz_renorm_template_plan
-// takes.  NGZ_OK or NGZ_E_INVALID
-int parse_template(const uint8_t *tmpl, size_t len, int proto, bool options, std::vector<PlanField> *out);
-
 }  // namespace ngzo

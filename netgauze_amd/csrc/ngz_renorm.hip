@@ -15,6 +15,8 @@
 #include "ngz_host.h"
 #include "ngz_renorm_internal.h"
 #include "ngz_renorm_math.h"
+#include "ngz_stage.h"
+#include "ngz_template_record.h"
 
 namespace {
 
@@ -54,34 +56,12 @@ int param_index(uint16_t ie, uint16_t *width) {
 }
 bool is_count_ie(uint16_t ie) { return ie == 1 || ie == 2 || ie == 85 || ie == 86; }
 
-__device__ __forceinline__ uint64_t rn_wave_sum(uint64_t v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-
-// four consecutive rows of a 1-, 2- or 4-byte column (r0 a multiple of 4: one aligned vector load)
-__device__ __forceinline__ void rn_load4(const uint8_t *col, uint32_t w, uint32_t r0, uint32_t v[4]) {
-    if (w == 4) {
-        const uint4 x = *(const uint4 *)(col + 4ull * r0);
-        v[0] = x.x; v[1] = x.y; v[2] = x.z; v[3] = x.w;
-    } else if (w == 2) {
-        const uint2 x = *(const uint2 *)(col + 2ull * r0);
-        v[0] = x.x & 0xFFFFu; v[1] = x.x >> 16; v[2] = x.y & 0xFFFFu; v[3] = x.y >> 16;
-    } else {
-        const uint32_t x = *(const uint32_t *)(col + r0);
-        v[0] = x & 0xFFu; v[1] = (x >> 8) & 0xFFu; v[2] = (x >> 16) & 0xFFu; v[3] = x >> 24;
-    }
-}
-
 // Bit masks of the parameters by column width
 constexpr uint32_t RN_W1 = (1u << NGZ_RN_P35) | (1u << NGZ_RN_P49);
 constexpr uint32_t RN_W2 = 1u << NGZ_RN_P304;
 
 __global__ __launch_bounds__(RN_THREADS) void k_renorm(const RnPlan P) {
     __shared__ unsigned long long acc[RN_STATS];
-    if (threadIdx.x < RN_STATS) acc[threadIdx.x] = 0;
-    __syncthreads();
     uint32_t n_renorm = 0, n_invalid = 0, n_inferred = 0;
     const uint32_t quads = (P.n_rows + RN_ROWS_PER_LANE - 1) / RN_ROWS_PER_LANE;
     for (uint32_t q = blockIdx.x * RN_THREADS + threadIdx.x; q < quads; q += gridDim.x * RN_THREADS) {
@@ -99,7 +79,7 @@ __global__ __launch_bounds__(RN_THREADS) void k_renorm(const RnPlan P) {
 #define RN_PARAM(IDX, MEMBER)                                                                       \
     if (P.present & (1u << (IDX))) {                                                                \
         uint32_t v[4];                                                                              \
-        rn_load4(P.param[IDX], ((1u << (IDX)) & RN_W1) ? 1u : ((1u << (IDX)) & RN_W2) ? 2u : 4u, r0, v); \
+        ngzs::load4(P.param[IDX], ((1u << (IDX)) & RN_W1) ? 1u : ((1u << (IDX)) & RN_W2) ? 2u : 4u, r0, v); \
         prm[0].MEMBER = v[0]; prm[1].MEMBER = v[1]; prm[2].MEMBER = v[2]; prm[3].MEMBER = v[3];      \
     }
         RN_PARAM(NGZ_RN_P34, interval34)
@@ -130,7 +110,7 @@ __global__ __launch_bounds__(RN_THREADS) void k_renorm(const RnPlan P) {
                     const double2 b = *(const double2 *)(P.ov_col[o] + 8ull * r0 + 16);
                     dv[0] = a.x; dv[1] = a.y; dv[2] = b.x; dv[3] = b.y;
                 } else {
-                    rn_load4(P.ov_col[o], ((1u << pi) & RN_W1) ? 1u : ((1u << pi) & RN_W2) ? 2u : 4u, r0, v);
+                    ngzs::load4(P.ov_col[o], ((1u << pi) & RN_W1) ? 1u : ((1u << pi) & RN_W2) ? 2u : 4u, r0, v);
                 }
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
@@ -187,14 +167,9 @@ __global__ __launch_bounds__(RN_THREADS) void k_renorm(const RnPlan P) {
         // the flags of four rows in one dword store
         *(uint32_t *)(P.flags + r0) = (flagged & 1u) | ((flagged & 2u) << 7) | ((flagged & 4u) << 14) | ((flagged & 8u) << 21);
     }
-    const uint64_t s0 = rn_wave_sum(n_renorm), s1 = rn_wave_sum(n_invalid), s2 = rn_wave_sum(n_inferred);
-    if ((threadIdx.x & 63) == 0) {
-        if (s0) atomicAdd(&acc[0], (unsigned long long)s0);
-        if (s1) atomicAdd(&acc[1], (unsigned long long)s1);
-        if (s2) atomicAdd(&acc[2], (unsigned long long)s2);
-    }
-    __syncthreads();
-    if (threadIdx.x < RN_STATS && acc[threadIdx.x]) atomicAdd(&P.stats[threadIdx.x], acc[threadIdx.x]);
+    const uint64_t cnt[RN_STATS] = {n_renorm, n_invalid, n_inferred};
+    unsigned long long *const dst[RN_STATS] = {&P.stats[0], &P.stats[1], &P.stats[2]};
+    ngzs::block_add<RN_STATS>(acc, cnt, dst);
 }
 
 // Rows of messages that did not decode (the final status is on the device after decode, k_counts;
@@ -204,14 +179,8 @@ __global__ void k_renorm_sets(const ngz_set_info *__restrict__ sets, uint32_t n_
                               uint32_t n_dgrams, uint32_t n_slots, const uint32_t *__restrict__ slot_rows,
                               const uint32_t *__restrict__ bm_off, uint32_t *__restrict__ bitmap,
                               unsigned long long *__restrict__ bad_rows, unsigned int *__restrict__ err) {
-    for (uint32_t s = blockIdx.x * blockDim.x + threadIdx.x; s < n_sets; s += gridDim.x * blockDim.x) {
-        const ngz_set_info si = sets[s];
-        if (!si.n) continue;
-        if (si.dgram >= n_dgrams || si.slot >= n_slots || (uint64_t)si.rec0 + si.n > slot_rows[si.slot]) {
-            atomicOr(err, 1u);
-            continue;
-        }
-        if (hdr[si.dgram].status == NGZ_DG_OK) continue;
+    ngzs::for_each_set(sets, n_sets, hdr, n_dgrams, n_slots, slot_rows, err, [&](uint32_t, const ngz_set_info &si, const ngz_dgram_hdr &h) {
+        if (h.status == NGZ_DG_OK) return;
         atomicAdd(&bad_rows[si.slot], (unsigned long long)si.n);
         uint32_t *bm = bitmap + bm_off[si.slot];
         uint32_t r = si.rec0;
@@ -223,7 +192,7 @@ __global__ void k_renorm_sets(const ngz_set_info *__restrict__ sets, uint32_t n_
             atomicOr(&bm[w], mask);
             r = (w + 1u) << 5;
         }
-    }
+    });
 }
 
 // One field of a template as the plan builder sees it
@@ -259,9 +228,8 @@ bool build_plan(const std::vector<PlanField> &fields, ngz_renorm_plan *out) {
 
 }  // namespace
 
-struct ngz_renorm {
-    int device = 0;
-    std::string last_error;
+struct ngz_renorm : ngzs::Stage {
+    ngz_renorm() : Stage(2) {}
     ngz_renorm_stats totals{};
     std::map<const ngz_ctx *, uint64_t> applied;  // context -> batch serial last applied
     // the batch last applied
@@ -273,40 +241,10 @@ struct ngz_renorm {
     ngzh::DevBuf<uint32_t> d_bitmap;
     ngzh::DevBuf<uint32_t> d_meta;               // slot_rows[S], bm_off[S]
     ngzh::DevBuf<unsigned long long> d_counters;  // stats[RN_STATS], err, bad_rows[S]
-    uint32_t *h_meta = nullptr;                   // pinned
-    size_t h_meta_cap = 0;
-    unsigned long long *h_counters = nullptr;     // pinned
-    size_t h_counters_cap = 0;
-    hipEvent_t ev[2]{};
+    ngzs::PinnedBuf<uint32_t> h_meta;
+    ngzs::PinnedBuf<unsigned long long> h_counters;
     float apply_ms = 0;
-    int n_cus = 256;
 };
-
-namespace {
-
-int rfail(ngz_renorm *r, int rc, const std::string &msg) {
-    if (r) r->last_error = msg;
-    return rc;
-}
-
-#define RN_HIP(r, x)                                                                            \
-    do {                                                                                        \
-        hipError_t e_ = (x);                                                                    \
-        if (e_ != hipSuccess) return rfail(r, NGZ_E_DEVICE, std::string(#x) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
-template <class T>
-int pinned_reserve(T **p, size_t *cap, size_t n) {
-    if (n <= *cap) return 0;
-    if (*p) hipHostFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    if (hipHostMalloc((void **)p, n * sizeof(T), hipHostMallocDefault) != hipSuccess) return -1;
-    *cap = n;
-    return 0;
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -315,16 +253,10 @@ int ngz_renorm_abi_version(void) { return NGZ_RENORM_ABI_VERSION; }
 int ngz_renorm_create(int device, ngz_renorm **out) {
     if (!out) return NGZ_E_INVALID;
     *out = nullptr;
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || device < 0 || device >= n) return NGZ_E_DEVICE;
-    if (hipSetDevice(device) != hipSuccess) return NGZ_E_DEVICE;
     ngz_renorm *r = new ngz_renorm;
     r->device = device;
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0)
-        r->n_cus = prop.multiProcessorCount;
-    if (hipEventCreate(&r->ev[0]) != hipSuccess || hipEventCreate(&r->ev[1]) != hipSuccess) {
-        ngz_renorm_destroy(r);
+    if (ngzs::device_init(r)) {  // a renormalizer takes its device at creation
+        delete r;
         return NGZ_E_DEVICE;
     }
     *out = r;
@@ -338,10 +270,6 @@ void ngz_renorm_destroy(ngz_renorm *r) {
     r->d_bitmap.release();
     r->d_meta.release();
     r->d_counters.release();
-    if (r->h_meta) hipHostFree(r->h_meta);
-    if (r->h_counters) hipHostFree(r->h_counters);
-    for (hipEvent_t e : r->ev)
-        if (e) hipEventDestroy(e);
     delete r;
 }
 
@@ -354,16 +282,15 @@ static int renorm_apply(ngz_renorm *r, const std::vector<ngze::SlotResult> *enri
                         ngz_renorm_stats *batch_stats, void *hip_stream) {
     if (!r || !ctx || !out) return NGZ_E_INVALID;
     if (batch_stats) memset(batch_stats, 0, sizeof *batch_stats);
-    if (ctx->device != r->device) return rfail(r, NGZ_E_INVALID, "the context is on another device");
-    if (ctx->async.pending.load()) return rfail(r, NGZ_E_INVALID, "a submitted decode is pending on the context");
+    if (int rc = ngzs::check_ctx(r, ctx)) return rc;
     {
         auto it = r->applied.find(ctx);
         if (it != r->applied.end() && it->second == ctx->batch_serial)
-            return rfail(r, NGZ_E_INVALID, "this batch was already renormalized");
+            return ngzs::fail(r, NGZ_E_INVALID, "this batch was already renormalized");
     }
     const uint32_t S = out->n_slots, D = out->n_dgrams, NS = out->n_sets;
-    if (S > NGZ_MAX_SLOTS || (S && !out->slots)) return rfail(r, NGZ_E_INVALID, "slot table");
-    RN_HIP(r, hipSetDevice(r->device));
+    if (!ngzs::slot_table_ok(out)) return ngzs::fail(r, NGZ_E_INVALID, "slot table");
+    NGZ_STAGE_HIP(r, hipSetDevice(r->device));
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
 
     // per-slot plans from the slot's column layout; nothing is launched before every slot checked out
@@ -387,10 +314,8 @@ static int renorm_apply(ngz_renorm *r, const std::vector<ngze::SlotResult> *enri
         flag_bytes += ((uint64_t)si.n_records + 15) & ~15ull;  // 16-byte aligned, room for a last quad
         bm_words += ((uint64_t)si.n_records + 31) / 32 + 1;
         if (!si.n_records) continue;
-        const int nf = ngz_slot_fields(ctx, s, nullptr, 0);
-        if (nf < 0) return rfail(r, NGZ_E_INVALID, "ngz_slot_fields: not the context's last batch");
-        fi.resize(std::max(nf, 1));
-        ngz_slot_fields(ctx, s, fi.data(), (uint32_t)nf);
+        const int nf = ngzs::slot_fields(r, ctx, s, fi);
+        if (nf < 0) return nf;
         pf.resize(nf);
         for (int i = 0; i < nf; ++i) {
             uint16_t pw = 0;
@@ -399,7 +324,7 @@ static int renorm_apply(ngz_renorm *r, const std::vector<ngze::SlotResult> *enri
             pf[i] = PlanField{fi[i].pen, fi[i].ie_id, fi[i].is_scope != 0, fi[i].kind == NGZ_K_UINT && fi[i].width == want};
         }
         if (!build_plan(pf, &w.plan))
-            return rfail(r, NGZ_E_LIMIT, "a template with more than 64 count fields");
+            return ngzs::fail(r, NGZ_E_LIMIT, "a template with more than 64 count fields");
         // the enrichment's added columns of sampling IEs (canonical encoding: NGZ_K_UINT of the IE's width)
         if (enriched && !w.plan.dropped && s < enriched->size() && (*enriched)[s].rows == si.n_records) {
             const ngze::SlotResult &er = (*enriched)[s];
@@ -407,7 +332,7 @@ static int renorm_apply(ngz_renorm *r, const std::vector<ngze::SlotResult> *enri
                 uint16_t pw = 0;
                 const int pi = er.cols[c].pen == 0 ? param_index(er.cols[c].ie_id, &pw) : -1;
                 if (pi < 0 || er.cols[c].kind != NGZ_K_UINT || er.cols[c].width != pw || !er.cols[c].data) continue;
-                if (w.k.n_ov == RN_MAX_OV) return rfail(r, NGZ_E_LIMIT, "more than 16 added sampling columns in one slot");
+                if (w.k.n_ov == RN_MAX_OV) return ngzs::fail(r, NGZ_E_LIMIT, "more than 16 added sampling columns in one slot");
                 w.k.ov_col[w.k.n_ov] = er.cols[c].data;
                 w.k.ov_param[w.k.n_ov] = (uint8_t)pi;
                 w.k.ov_bit[w.k.n_ov] = (uint8_t)c;
@@ -416,14 +341,14 @@ static int renorm_apply(ngz_renorm *r, const std::vector<ngze::SlotResult> *enri
             if (w.k.n_ov) {
                 size_t n_count_fields = 0;
                 for (const PlanField &f : pf) n_count_fields += !f.scope && f.pen == 0 && f.usable && is_count_ie(f.ie);
-                if (n_count_fields > NGZ_RENORM_MAX_COUNTS) return rfail(r, NGZ_E_LIMIT, "a template with more than 64 count fields");
+                if (n_count_fields > NGZ_RENORM_MAX_COUNTS) return ngzs::fail(r, NGZ_E_LIMIT, "a template with more than 64 count fields");
                 w.k.ov_mask = er.mask;
                 w.plan.launches = 1;
             }
         }
         if (!w.plan.launches) continue;
         if (!si.columns || ((uintptr_t)si.columns & 15) || (si.capacity & 3) || si.capacity < si.n_records)
-            return rfail(r, NGZ_E_LIMIT, "unexpected column block alignment");
+            return ngzs::fail(r, NGZ_E_LIMIT, "unexpected column block alignment");
         for (int i = 0; i < NGZ_RN_NPARAMS; ++i) {
             if (w.plan.param_field[i] < 0) continue;
             w.k.param[i] = si.columns + (uint64_t)si.capacity * fi[w.plan.param_field[i]].col_off;
@@ -434,12 +359,11 @@ static int renorm_apply(ngz_renorm *r, const std::vector<ngze::SlotResult> *enri
         w.k.n_counts = w.plan.n_counts;
         w.k.n_rows = si.n_records;
     }
-    if (flag_bytes >> 32 || bm_words >> 32) return rfail(r, NGZ_E_LIMIT, "batch too large");
+    if (flag_bytes >> 32 || bm_words >> 32) return ngzs::fail(r, NGZ_E_LIMIT, "batch too large");
     const size_t n_counters = RN_STATS + 1 + S;
     if (r->d_flags.ensure(flag_bytes + 16) || r->d_bitmap.ensure(bm_words + 1) || r->d_meta.ensure(2ull * S + 2) ||
-        r->d_counters.ensure(n_counters) || pinned_reserve(&r->h_meta, &r->h_meta_cap, 2ull * S + 2) ||
-        pinned_reserve(&r->h_counters, &r->h_counters_cap, n_counters))
-        return rfail(r, NGZ_E_NOMEM, "renormalizer buffers");
+        r->d_counters.ensure(n_counters) || r->h_meta.reserve(2ull * S + 2) || r->h_counters.reserve(n_counters))
+        return ngzs::fail(r, NGZ_E_NOMEM, "renormalizer buffers");
     // from here on the batch counts as applied: the columns may change
     r->applied[ctx] = ctx->batch_serial;
     r->last_ctx = ctx;
@@ -450,20 +374,20 @@ static int renorm_apply(ngz_renorm *r, const std::vector<ngze::SlotResult> *enri
     ctx->json_view.reset();
 
     for (uint32_t s = 0; s < S; ++s) {
-        r->h_meta[s] = slot_rows[s];
-        r->h_meta[S + s] = bm_off[s];
+        r->h_meta.p[s] = slot_rows[s];
+        r->h_meta.p[S + s] = bm_off[s];
     }
-    RN_HIP(r, hipEventRecord(r->ev[0], st));
-    if (S) RN_HIP(r, hipMemcpyAsync(r->d_meta.p, r->h_meta, 2ull * S * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    RN_HIP(r, hipMemsetAsync(r->d_counters.p, 0, n_counters * sizeof(unsigned long long), st));
-    RN_HIP(r, hipMemsetAsync(r->d_bitmap.p, 0, (bm_words + 1) * sizeof(uint32_t), st));
+    NGZ_STAGE_HIP(r, hipEventRecord(r->ev[0], st));
+    if (S) NGZ_STAGE_HIP(r, hipMemcpyAsync(r->d_meta.p, r->h_meta.p, 2ull * S * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    NGZ_STAGE_HIP(r, hipMemsetAsync(r->d_counters.p, 0, n_counters * sizeof(unsigned long long), st));
+    NGZ_STAGE_HIP(r, hipMemsetAsync(r->d_bitmap.p, 0, (bm_words + 1) * sizeof(uint32_t), st));
     unsigned long long *d_stats = r->d_counters.p, *d_bad = r->d_counters.p + RN_STATS + 1;
     unsigned int *d_err = (unsigned int *)(r->d_counters.p + RN_STATS);
     if (NS && D && S) {
         const uint32_t nb = (uint32_t)std::min<uint64_t>(((uint64_t)NS + 255) / 256, (uint64_t)r->n_cus * 8);
         hipLaunchKernelGGL(k_renorm_sets, dim3(nb), dim3(256), 0, st, out->sets, NS, out->dgrams, D, S, r->d_meta.p,
                            r->d_meta.p + S, r->d_bitmap.p, d_bad, d_err);
-        RN_HIP(r, hipGetLastError());
+        NGZ_STAGE_HIP(r, hipGetLastError());
     }
     uint32_t launches = 0;
     for (uint32_t s = 0; s < S; ++s) {
@@ -471,7 +395,7 @@ static int renorm_apply(ngz_renorm *r, const std::vector<ngze::SlotResult> *enri
         if (!slot_rows[s]) continue;
         uint8_t *flags = r->d_flags.p + flag_off[s];
         if (!w.plan.launches) {  // its flags read 0
-            RN_HIP(r, hipMemsetAsync(flags, 0, ((uint64_t)slot_rows[s] + 15) & ~15ull, st));
+            NGZ_STAGE_HIP(r, hipMemsetAsync(flags, 0, ((uint64_t)slot_rows[s] + 15) & ~15ull, st));
             continue;
         }
         w.k.flags = flags;
@@ -480,21 +404,22 @@ static int renorm_apply(ngz_renorm *r, const std::vector<ngze::SlotResult> *enri
         const uint64_t quads = ((uint64_t)slot_rows[s] + RN_ROWS_PER_LANE - 1) / RN_ROWS_PER_LANE;
         const uint32_t nb = (uint32_t)std::min<uint64_t>((quads + RN_THREADS - 1) / RN_THREADS, (uint64_t)r->n_cus * 16);
         hipLaunchKernelGGL(k_renorm, dim3(nb), dim3(RN_THREADS), 0, st, w.k);
-        RN_HIP(r, hipGetLastError());
+        NGZ_STAGE_HIP(r, hipGetLastError());
         ++launches;
     }
-    RN_HIP(r, hipEventRecord(r->ev[1], st));
-    RN_HIP(r, hipMemcpyAsync(r->h_counters, r->d_counters.p, n_counters * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    RN_HIP(r, hipStreamSynchronize(st));
-    if (launches) RN_HIP(r, hipEventElapsedTime(&r->apply_ms, r->ev[0], r->ev[1]));
-    if (r->h_counters[RN_STATS] & 1) return rfail(r, NGZ_E_INVALID, "a data set outside the batch's tables: `out` is not the context's last decode");
+    NGZ_STAGE_HIP(r, hipEventRecord(r->ev[1], st));
+    NGZ_STAGE_HIP(r, hipMemcpyAsync(r->h_counters.p, r->d_counters.p, n_counters * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    NGZ_STAGE_HIP(r, hipStreamSynchronize(st));
+    if (launches) NGZ_STAGE_HIP(r, hipEventElapsedTime(&r->apply_ms, r->ev[0], r->ev[1]));
+    const unsigned long long *hc = r->h_counters.p;
+    if (hc[RN_STATS] & 1) return ngzs::fail_sets(r);
     ngz_renorm_stats bs{};
-    bs.flows_renormalized = r->h_counters[0];
-    bs.ie_missing_or_invalid = r->h_counters[1];
-    bs.sampling_algorithm_inferred = r->h_counters[2];
+    bs.flows_renormalized = hc[0];
+    bs.ie_missing_or_invalid = hc[1];
+    bs.sampling_algorithm_inferred = hc[2];
     for (uint32_t s = 0; s < S; ++s) {
         if (!slot_rows[s]) continue;
-        const uint64_t ok_rows = slot_rows[s] - std::min<uint64_t>(slot_rows[s], r->h_counters[RN_STATS + 1 + s]);
+        const uint64_t ok_rows = ngzs::ok_rows(slot_rows[s], hc[RN_STATS + 1 + s]);
         if (work[s].plan.dropped) bs.records_dropped += ok_rows;
         else bs.flows_processed += ok_rows;
     }
@@ -519,8 +444,8 @@ int ngz_renorm_apply_enriched(ngz_renorm *r, ngz_enrich *e, ngz_ctx *ctx, const 
     if (!r || !e || !ctx || !out) return NGZ_E_INVALID;
     if (batch_stats) memset(batch_stats, 0, sizeof *batch_stats);
     const std::vector<ngze::SlotResult> *res = ngze::results_for(e, ctx);
-    if (ngze::enrich_device(e) != r->device) return rfail(r, NGZ_E_INVALID, "the enricher is on another device");
-    if (!res) return rfail(r, NGZ_E_INVALID, "the enricher has not applied the context's last batch");
+    if (ngze::enrich_device(e) != r->device) return ngzs::fail(r, NGZ_E_INVALID, "the enricher is on another device");
+    if (!res) return ngzs::fail(r, NGZ_E_INVALID, "the enricher has not applied the context's last batch");
     return renorm_apply(r, res, ctx, out, batch_stats, hip_stream);
 }
 
@@ -533,7 +458,7 @@ int ngz_renorm_totals(ngz_renorm *r, ngz_renorm_stats *totals, int reset) {
 
 int ngz_renorm_flags(ngz_renorm *r, uint32_t slot, const uint8_t **dev_flags, uint32_t *n) {
     if (!r || !dev_flags || !n) return NGZ_E_INVALID;
-    if (!r->last_ctx || slot >= r->slot_rows.size()) return rfail(r, NGZ_E_INVALID, "no such slot in the batch last applied");
+    if (!r->last_ctx || slot >= r->slot_rows.size()) return ngzs::fail(r, NGZ_E_INVALID, "no such slot in the batch last applied");
     *dev_flags = r->d_flags.p + r->flag_off[slot];
     *n = r->slot_rows[slot];
     return NGZ_OK;
@@ -543,13 +468,13 @@ int ngz_renorm_flags(ngz_renorm *r, uint32_t slot, const uint8_t **dev_flags, ui
 
 int ngzh::renorm_flags_host(ngz_renorm *r, ngz_ctx *ctx, std::vector<uint8_t> &flags, std::vector<const uint8_t *> &slot_flags) {
     if (r->last_ctx != ctx || r->last_serial != ctx->batch_serial || ctx->async.pending.load())
-        return rfail(r, NGZ_E_INVALID, "the context's last batch is not the batch last applied");
-    RN_HIP(r, hipSetDevice(r->device));
+        return ngzs::fail(r, NGZ_E_INVALID, "the context's last batch is not the batch last applied");
+    NGZ_STAGE_HIP(r, hipSetDevice(r->device));
     const size_t S = r->slot_rows.size();
-    if (S != ctx->slot_infos.size()) return rfail(r, NGZ_E_INVALID, "slot table");
+    if (S != ctx->slot_infos.size()) return ngzs::fail(r, NGZ_E_INVALID, "slot table");
     const uint64_t total = S ? r->flag_off[S - 1] + (((uint64_t)r->slot_rows[S - 1] + 15) & ~15ull) : 0;
     flags.assign(total + 1, 0);
-    if (total) RN_HIP(r, hipMemcpy(flags.data(), r->d_flags.p, total, hipMemcpyDeviceToHost));
+    if (total) NGZ_STAGE_HIP(r, hipMemcpy(flags.data(), r->d_flags.p, total, hipMemcpyDeviceToHost));
     slot_flags.assign(S, nullptr);
     for (size_t s = 0; s < S; ++s)
         if (r->slot_rows[s]) slot_flags[s] = flags.data() + r->flag_off[s];
@@ -565,7 +490,7 @@ int64_t ngz_renorm_batch_json(ngz_renorm *r, ngz_ctx *ctx, const uint8_t *host_b
     if (const int frc = ngzh::renorm_flags_host(r, ctx, flags, mode.slot_flags)) return frc;
     ngzh::JsonView v;
     const int rc = ngzh::json_view_load(ctx, host_bytes, v);
-    if (rc) return rfail(r, rc, "json_view_load");
+    if (rc) return ngzs::fail(r, rc, "json_view_load");
     int64_t lines = 0;
     std::string s;
     for (uint32_t d = 0; d < ctx->last_in.n; ++d) {
@@ -591,50 +516,18 @@ int ngz_renorm_template_plan(const uint8_t *tmpl, size_t len, int proto, ngz_ren
     const bool options = (proto & NGZ_RENORM_OPTIONS) != 0;
     proto &= ~NGZ_RENORM_OPTIONS;
     if (proto != 10 && proto != 9) return NGZ_E_INVALID;
-    size_t pos = 2;  // template id
-    uint32_t n_fields = 0, n_scope = 0;
-    size_t scope_end = 0, end = len;  // NetFlow v9 options: byte lengths
-    if (!options) {
-        if (len < 4) return NGZ_E_INVALID;
-        n_fields = ngzh::rd16(tmpl + 2);
-        pos = 4;
-    } else {
-        if (len < 6) return NGZ_E_INVALID;
-        pos = 6;
-        if (proto == 10) {  // field count (scope included), scope field count
-            n_fields = ngzh::rd16(tmpl + 2);
-            n_scope = ngzh::rd16(tmpl + 4);
-            if (n_scope > n_fields) return NGZ_E_INVALID;
-        } else {  // scope bytes, option bytes
-            scope_end = pos + ngzh::rd16(tmpl + 2);
-            end = scope_end + ngzh::rd16(tmpl + 4);
-            if (end > len) return NGZ_E_INVALID;
-        }
-    }
     std::vector<PlanField> pf;
-    const bool by_bytes = options && proto == 9;
-    while (by_bytes ? pos < end : pf.size() < n_fields) {
-        if (pos + 4 > len) return NGZ_E_INVALID;
-        uint32_t code = ngzh::rd16(tmpl + pos);
-        const uint32_t L = ngzh::rd16(tmpl + pos + 2);
-        pos += 4;
-        const bool scope = by_bytes ? pos - 4 < scope_end : pf.size() < n_scope;
-        uint32_t pen = 0;
-        if (!(by_bytes && scope) && (code & 0x8000)) {  // NetFlow v9 scope codes are raw
-            if (pos + 4 > len) return NGZ_E_INVALID;
-            pen = ngzh::rd32(tmpl + pos);
-            pos += 4;
-            code &= 0x7FFF;
-        }
+    const int rc = ngzt::walk_template_record(tmpl, len, proto, options, [&](const ngzt::FieldSpec &f) {
+        const uint32_t L = f.length;
         uint16_t pw = 0;
-        const int pi = pen == 0 ? param_index((uint16_t)code, &pw) : -1;
+        const int pi = f.pen == 0 ? param_index(f.ie, &pw) : -1;
         // the lengths field_rule decodes into the IE's full-width column (reduced-size encoding)
         bool usable = false;
         if (pi >= 0) usable = pw == 8 ? L == 8 : pw == 1 ? L == 1 : (L >= 1 && L <= pw);
-        else if (pen == 0 && is_count_ie((uint16_t)code)) usable = L >= 1 && L <= 8;
-        pf.push_back(PlanField{pen, (uint16_t)code, scope, usable});
-        if (pf.size() > 0x7FFF) return NGZ_E_INVALID;
-    }
+        else if (f.pen == 0 && is_count_ie(f.ie)) usable = L >= 1 && L <= 8;
+        pf.push_back(PlanField{f.pen, f.ie, f.scope, usable});
+    });
+    if (rc) return rc;
     build_plan(pf, out);
     return NGZ_OK;
 }
