@@ -2715,7 +2715,14 @@ __global__ void k_agg_compact(const unsigned long long *__restrict__ tags, uint8
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
-struct ngz_agg {
+struct AggDicts {  // what a push adds to on the host, and a failed push puts back (PushUndo)
+    // fixed at first sight: column width and decoded kind of every key / value
+    std::vector<int> val_w, key_w, key_kind_seen, val_kind_seen;
+    // dictionaries: entry = value, -1 = free (bits of groups refer to entry positions)
+    std::vector<int64_t> templates, ports, domains;
+};
+
+struct ngz_agg : AggDicts {
     int device = 0;
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -2729,10 +2736,6 @@ struct ngz_agg {
     uint64_t limit = 0;      // groups held at most (the capacity asked for)
     uint64_t live = 0, tombs = 0;
     AggParams P{};
-    // fixed at first sight: column width and decoded kind of every key / value
-    std::vector<int> val_w, key_w, key_kind_seen, val_kind_seen;
-    // dictionaries: entry = value, -1 = free (bits of groups refer to entry positions)
-    std::vector<int64_t> templates, ports, domains;
     // the dictionaries as of the last flush / emit (the rows it returned refer to them)
     std::vector<int64_t> out_templates, out_ports, out_domains;
     // exporter peers: the IP keys groups and windows (aggregator.rs:119-124, aggregation.rs:96-108);
@@ -2772,14 +2775,14 @@ struct ngz_agg {
     uint8_t *enr_buf = nullptr;
     uint64_t enr_cap = 0;
     // scratch, grown on demand
-    void *scratch = nullptr;
+    uint8_t *scratch = nullptr;
     size_t scratch_cap = 0;
     uint8_t *rec_buf = nullptr;  // record contexts, rec_g, claims, collided lists, sort buffers
     size_t rec_cap = 0;
     uint8_t *part_buf = nullptr;  // partitioned reduction: counts, offsets, scan scratch, payloads
     size_t part_cap = 0;
     LcEntry *lc = nullptr;        // low-cardinality path: the waves' partial groups
-    uint32_t lc_cap = 0;          // ... entries allocated
+    uint32_t lc_cap = 0;          // ... entries allocated, the merge workgroups' slices after them included
     unsigned int *lc_cnt = nullptr;  // [0] entries written, [1] overflow flag, [2] merge workgroups done
     LcSet *lc_sets = nullptr;     // ... the push's set descriptors
     uint32_t lc_sets_cap = 0;
@@ -3042,7 +3045,6 @@ int64_t take_rows(ngz_agg *a, void *dst, uint64_t cap, const int64_t *cut, bool 
         uint8_t *tails = nullptr;
         unsigned long long nt = 0;
         hipError_t e = hipSuccess;
-        a->out_tails.clear();
         if (a->arena_mark) {
             e = hipMalloc(&tails, a->arena_mark);
             if (e == hipSuccess) e = hipMemsetAsync(a->arena_used + 1, 0, 8, a->stream);
@@ -3071,6 +3073,19 @@ int64_t take_rows(ngz_agg *a, void *dst, uint64_t cap, const int64_t *cut, bool 
     return (int64_t)n;
 }
 
+// Device buffer of at least need_elems elements, grown on demand to exactly that many (the pushes'
+// buffers follow the batch's sizes: no slack).  false: out of memory, and the buffer is gone
+template <class T, class C>
+bool grow(T *&p, C &cap, size_t need_elems) {
+    if (need_elems <= cap) return true;
+    hipFree(p);
+    p = nullptr;
+    cap = 0;
+    if (hipMalloc(&p, need_elems * sizeof(T)) != hipSuccess) { p = nullptr; return false; }
+    cap = (C)need_elems;
+    return true;
+}
+
 int64_t floordiv64(int64_t x, int64_t d) { return x / d - ((x % d != 0) && ((x < 0) != (d < 0))); }
 
 // Windows a peer's event time has closed (aggregation.rs:154-160): starts <= cutoff =
@@ -3093,22 +3108,26 @@ int upload_cutoffs(ngz_agg *a, bool *any) {
         *any = *any || c[i] != INT64_MIN;
     }
     if (!*any) return NGZ_OK;
-    if (n > a->cut_cap) {
-        hipFree(a->cut);
-        a->cut = nullptr;
-        a->cut_cap = 0;
-        const uint32_t want = std::max<uint32_t>(n, 64);
-        if (hipMalloc(&a->cut, 8ull * want) != hipSuccess) return fail(a, NGZ_E_NOMEM, "cutoff table");
-        a->cut_cap = want;
-    }
+    if (!grow(a->cut, a->cut_cap, std::max<uint32_t>(n, 64))) return fail(a, NGZ_E_NOMEM, "cutoff table");
     AGG_HIP(a, hipMemcpyAsync(a->cut, c.data(), 8ull * n, hipMemcpyHostToDevice, a->stream));
     return NGZ_OK;
 }
 
-void forget_peers(ngz_agg *a) {
+// every group, peer and dictionary entry gone (flush / reset); synchronises
+int clear_all(ngz_agg *a) {
     a->peers.clear();
     a->peer_time.clear();
     a->peer_index.clear();
+    a->templates.clear();
+    a->ports.clear();
+    a->domains.clear();
+    a->live = a->tombs = 0;
+    int rc = reset_rows(a, a->tags, a->rows);
+    if (rc == NGZ_OK) rc = upload_domains(a);
+    if (rc == NGZ_OK) rc = arena_clear(a);
+    if (rc != NGZ_OK) return rc;
+    AGG_HIP(a, hipStreamSynchronize(a->stream));
+    return NGZ_OK;
 }
 
 std::string peer_key(const ngz_peer &p) {
@@ -3378,6 +3397,48 @@ int ngz_agg_layout(ngz_agg *a, uint32_t *row_bytes, uint32_t *key_off, uint16_t 
     return NGZ_OK;
 }
 
+}  // extern "C"
+
+namespace {  // the push: phases over one PushState, in push_impl's order
+
+struct PushState;
+
+// What a refused push takes back.  The stage says how far the push has got and only advances:
+//   peer_only  a new peer's entry (the table rebuild before the snapshot failed)
+//   host       and the set dictionaries and first-sight widths / kinds, as `kept` has them
+//   domains    and the device's domain dictionary, which may hold the push's new domains
+//   claims     and the slots the push claimed and their key tails in the arena; synchronises
+// Two kinds of exit undo nothing, on purpose, and poison the aggregator until ngz_agg_reset: AGG_HIP (a HIP call
+// failed: the device's state is unknown) and the partition buffers' allocation failure (the claims are committed).
+struct PushUndo {
+    enum Stage { peer_only, host, domains, claims };
+    PushState *ps;
+    Stage stage;
+    bool new_peer;   // the push gave the peer IP its entry
+    std::string pk;  // ... under this key of peer_index
+    AggDicts kept;   // from stage host: the dictionaries as they were
+    int refuse(int rc, const std::string &why);  // undoes what the stage says, fails the push with (rc, why)
+};
+
+// enriched push: a slot with a resolve pass, and what of the aggregator's scratch it uses
+// (offsets into enr_buf until it is sized; the writer id sits at its start)
+struct EnrSlot {
+    uint32_t slot;
+    ngza::ResolvePlan rp;
+    uint64_t kpres_off, vpres_off;
+    bool sel_scratch[ngza::RS_MAX_SEL];  // the field has a resolved column, at sel_off
+    uint64_t sel_off[ngza::RS_MAX_SEL];
+};
+
+struct Loc {  // a selected field's column: the template's own, an added one, or a resolved one of the scratch
+    bool found = false;
+    uint8_t kind = 0;
+    uint32_t width = 0;
+    const uint8_t *col = nullptr;  // null for a resolved column: its address follows once the scratch is sized
+};
+
+constexpr uint64_t al(uint64_t x) { return (x + 255) & ~255ull; }
+
 // A record kernel's launch: its per-row instantiation (ENR) only in an enriched push with a field on
 // an added or resolved column; every other push launches the code without the presence loads
 #define AGG_LAUNCH_ENR(K, ...)                                      \
@@ -3391,24 +3452,111 @@ int ngz_agg_layout(ngz_agg *a, uint32_t *row_bytes, uint32_t *key_off, uint16_t 
         else hipLaunchKernelGGL((K<A, false>), __VA_ARGS__);           \
     } while (0)
 
-// ngz_agg_push, and with `enr` (an enricher's results for this batch) ngz_agg_push_enriched
-static int push_impl(ngz_agg *a, ngz_enrich *e, const std::vector<ngze::SlotResult> *enr, ngz_ctx *ctx,
-                     const ngz_batch_out *out, const ngz_peer *peer, int64_t collection_time_ms,
-                     uint64_t *late_records, void *hip_stream) {
-    if (!a || !ctx || !out || !peer || (peer->family != 4 && peer->family != 6)) return NGZ_E_INVALID;
-    if (late_records) *late_records = 0;
-    a->last_path = "none";  // no record to reduce (set below otherwise)
-    a->t_resolve = 0;
-    if (a->poisoned) return fail(a, NGZ_AGG_E_POISONED, "aggregator failed earlier: ngz_agg_reset it");
-    AGG_HIP(a, hipSetDevice(a->device));
-    if (hip_stream) AGG_HIP(a, hipStreamSynchronize((hipStream_t)hip_stream));
-    const uint16_t peer_port = peer->port;
-    // the peer IP's entry (a new IP gets the next one; taken back if the push fails)
-    const std::string pk = peer_key(*peer);
-    bool new_peer = false;
-    uint32_t pi;
-    {
-        auto it = a->peer_index.find(pk);
+// ngz_agg_push: occurrence f.index of the IE among the template's non-scope fields
+void locate_own(const ngz_slot_info &si, const ngz_field_info *fi, int nf, const ngz_agg_field &f, Loc &L) {
+    uint32_t seen = 0;
+    for (int i = 0; i < nf; ++i) {
+        const ngz_field_info &x = fi[i];
+        if (x.is_scope || x.pen != f.pen || x.ie_id != f.ie_id) continue;
+        if (seen++ == f.index) {
+            L = Loc{true, x.kind, x.width, si.columns + (uint64_t)si.capacity * x.col_off};
+            return;
+        }
+    }
+}
+
+// Key k on the column at f: the refusal, or nullptr with the plan and the first-sight width / kind set
+const char *accept_key(ngz_agg *a, AggSlotPlan &sp, uint32_t k, const Loc &f) {
+    if (a->P.key_kind[k] == KK_BYTES) {
+        // any length, fixed or variable-length (a record's text / bytes, BVAL)
+        if (f.kind == NGZ_K_FAIL) return "key field of a failing template";
+        if (f.kind == NGZ_K_VLEN) sp.key_vlen |= 1u << k;
+    } else {
+        if (f.kind == NGZ_K_VLEN || f.kind == NGZ_K_FAIL)
+            return "fixed-size key field sent variable-length (its records fail to decode)";
+        if (f.width > a->P.key_slot[k]) return "key field wider than its row slot";
+        if (a->P.packed && f.width != a->P.key_pw[k]) return "key column width differs from the IE's width";
+    }
+    sp.key_col[k] = f.col;
+    sp.key_w[k] = f.width;
+    if (a->key_w[k] < 0) a->key_w[k] = f.width;
+    if (a->key_kind_seen[k] < 0) a->key_kind_seen[k] = f.kind;
+    return nullptr;
+}
+
+// Aggregated field v likewise
+const char *accept_value(ngz_agg *a, AggSlotPlan &sp, uint32_t v, const Loc &f) {
+    const int vc = a->P.val_vc[v];
+    if ((vc == VC_VBYTES || vc == VC_VLIST) && f.kind != NGZ_K_FAIL) {
+        // Box<[u8]> values: any length, fixed or variable-length (BVAL)
+        if (f.kind == NGZ_K_VLEN) sp.val_vlen |= 1u << v;
+        if (a->val_w[v] < 0) a->val_w[v] = f.width;
+    } else {
+        if (f.kind == NGZ_K_VLEN || f.kind == NGZ_K_FAIL || (vc == VC_BYTES && f.width > 32))
+            return "fixed-size aggregated field sent variable-length (its records fail to decode)";
+        const bool int_like = vc == VC_UINT || vc == VC_SINT || vc == VC_RANK;
+        if ((int_like && f.width != 1 && f.width != 2 && f.width != 4 && f.width != 8) ||
+            (vc == VC_F32 && f.width != 4) || (vc == VC_F64 && f.width != 8) || (vc == VC_IPV6 && f.width != 16) ||
+            (vc == VC_DTFRAC && f.width != 8))
+            return "aggregated field of an unexpected column width";
+        if (a->val_w[v] >= 0 && a->val_w[v] != f.width) return "aggregated field width differs between templates";
+        a->val_w[v] = f.width;
+    }
+    if (a->val_kind_seen[v] < 0) a->val_kind_seen[v] = f.kind;
+    sp.val_col[v] = f.col;
+    sp.val_w[v] = f.width;
+    return nullptr;
+}
+
+struct PushState {  // members past `NS` start out zero (push_impl)
+    ngz_agg *a;
+    const ngz_batch_out *out;
+    const std::vector<ngze::SlotResult> *enr;  // ngz_agg_push_enriched: the enricher's results for this batch, else null
+    hipStream_t st;
+    uint32_t S, D, NS;
+    PushUndo undo;
+    bool gc_done;  // dict_gc ran for this push (put)
+    uint32_t pi;   // the peer IP's entry
+    int port_bit;
+    std::vector<AggSlotPlan> plans;
+    std::string writer;  // enriched push: the writer id, the enricher's value arena, the bytes of enr_buf
+    const uint8_t *enr_arena;
+    uint64_t enr_need;
+    std::vector<EnrSlot> enr_slots;
+    // the slot at hand (build_slot_plans); own_*: the selected fields on the template's own columns
+    uint32_t s, own_keys, own_vals;
+    int nf;
+    std::vector<ngz_field_info> fi;
+    std::vector<ngz_agg_slot_field> sfields;
+    std::vector<ngz_agg_ref> srefs;
+    bool enr_rows;  // some selected field is per row: the ENR kernels, the general path
+    AggParams P;    // a->P with this push's id, peer, port and owner choice
+    uint32_t *pm, *rstart, n_rec;  // of a->scratch: the event times, the sets' first records; the record count
+    uint16_t *dginfo;
+    unsigned int errv;
+    RecCtx C;
+    uint4 *sctx;  // of a->rec_buf
+    uint32_t *bset, *rec_g, *claims, *list_a, *list_b;
+    uint64_t R4, n_blk;
+    size_t B0, sort_tmp;
+    bool ordered;
+    uint32_t ig, fg;  // grids: bounded (workgroups walk tiles) / one tile per workgroup, all records in flight
+    unsigned long long n_claims;
+
+    int put(std::vector<int64_t> &d, int64_t x, uint32_t cap, int &bit) {
+        bit = dict_put(d, x, cap);
+        if (bit < 0 && !gc_done) {  // full: free the entries no live group uses, then retry
+            if (int r = dict_gc(a)) return r;
+            gc_done = true;
+            bit = dict_put(d, x, cap);
+        }
+        return NGZ_OK;
+    }
+
+    // The peer IP's entry (a new IP gets the next one), the table rebuild, the snapshot, the port's entry
+    int enter(const ngz_peer &peer) {
+        undo.pk = peer_key(peer);
+        auto it = a->peer_index.find(undo.pk);
         if (it != a->peer_index.end()) {
             pi = it->second;
         } else {
@@ -3418,488 +3566,308 @@ static int push_impl(ngz_agg *a, ngz_enrich *e, const std::vector<ngze::SlotResu
                              " distinct peer IPs since the last flush; entries are kept until ngz_agg_flush / "
                              "ngz_agg_reset, as each peer's event time is)"));
             pi = (uint32_t)a->peers.size();
-            ngz_peer p = *peer;
+            ngz_peer p = peer;
             if (p.family == 4) memset(p.addr + 4, 0, 12);
             p.reserved = 0;
             a->peers.push_back(p);
             a->peer_time.push_back(0);
-            a->peer_index.emplace(pk, pi);
-            new_peer = true;
+            a->peer_index.emplace(undo.pk, pi);
+            undo.new_peer = true;
         }
+        // tombstones of emitted windows are not reused by the probes: rebuild the table first when
+        // they and the most groups this push can add would crowd it
+        if (a->tombs && a->live + a->tombs + std::min<uint64_t>(out->n_records, a->limit - std::min(a->live, a->limit)) >
+                            a->slots / 4 * 3)
+            if (int r = rehash(a)) return undo.refuse(r, a->last_error);
+        undo.kept = *a;  // dictionaries as they were: a failed push puts them back
+        undo.stage = PushUndo::host;
+        if (int r = put(a->ports, peer.port, SET_BITS, port_bit)) return undo.refuse(r, a->last_error);
+        if (port_bit < 0) return undo.refuse(NGZ_AGG_E_OVERFLOW, "more than 64 peer ports in live windows");
+        return NGZ_OK;
     }
-    // tombstones of emitted windows are not reused by the probes: rebuild the table first when
-    // they and the most groups this push can add would crowd it
-    if (a->tombs && a->live + a->tombs + std::min<uint64_t>(out->n_records, a->limit - std::min(a->live, a->limit)) >
-                        a->slots / 4 * 3) {
-        if (int r = rehash(a)) {
-            if (new_peer) { a->peers.pop_back(); a->peer_time.pop_back(); a->peer_index.erase(pk); }
-            return r;
+
+    // ngz_agg_push_enriched: the field as the enrichment leaves it (past the own columns: the resolve pass)
+    int locate_enriched(const ngz_agg_field &f, bool is_value, uint32_t index, Loc &L) {
+        const ngz_slot_info &si = out->slots[s];
+        const ngze::SlotResult *er = &(*enr)[s];
+        ngz_agg_enrich_resolution res;
+        if (ngza::resolve_field(sfields.data(), (uint32_t)nf, srefs.data(), (uint32_t)er->cols.size(), f.pen, f.ie_id,
+                                f.index, &res))
+            return fail(a, NGZ_E_LIMIT, "more added columns than the aggregation takes");
+        if (res.kind == NGZ_AGG_RES_NONE) return NGZ_OK;
+        if (res.kind == NGZ_AGG_RES_OWN) {
+            const ngz_field_info &o = fi[res.own_field];
+            L = Loc{true, o.kind, o.width, si.columns + (uint64_t)si.capacity * o.col_off};
+            (is_value ? own_vals : own_keys) |= 1u << index;
+            return NGZ_OK;
         }
+        if (enr_slots.empty() || enr_slots.back().slot != s) {  // the slot's first field that needs the resolve pass
+            enr_slots.emplace_back();
+            EnrSlot &n = enr_slots.back();
+            memset(&n, 0, sizeof n);
+            n.slot = s;
+            n.rp.mask = er->mask;
+            n.rp.n_rows = si.n_records;
+            for (size_t c = 0; c < er->cols.size(); ++c) n.rp.col[c] = er->cols[c].data;
+            n.kpres_off = enr_need;
+            enr_need += al(4ull * si.n_records);
+            n.vpres_off = enr_need;
+            enr_need += al(4ull * si.n_records);
+        }
+        EnrSlot &n = enr_slots.back();
+        ngza::ResolveSel &sl = n.rp.sel[n.rp.n_sel];
+        sl.bit = (uint8_t)index;
+        sl.is_value = is_value ? 1 : 0;
+        sl.ordinal = res.ordinal;
+        sl.writer_after = res.kind == NGZ_AGG_RES_WRITER || res.writer_after;
+        sl.wid_len = (uint32_t)writer.size();
+        for (uint32_t c = 0; c < res.n_candidates; ++c) sl.cand |= 1u << res.candidates[c];
+        L.found = true;
+        if (res.kind == NGZ_AGG_RES_ADDED && res.n_candidates == 1 && !res.writer_after) {
+            const ngz_enrich_column &c = er->cols[res.candidates[0]];  // read in place
+            L.kind = c.kind;
+            L.width = c.width;
+            L.col = c.data;
+        } else {  // several candidates or the writer id: the chosen cell in a resolved column
+            L.kind = NGZ_K_VLEN;
+            L.width = 16;
+            for (uint32_t c = 0; c < res.n_candidates; ++c) {
+                const ngz_enrich_column &col = er->cols[res.candidates[c]];
+                if (c == 0 && !sl.writer_after) {
+                    L.kind = col.kind;
+                    L.width = col.width;
+                }
+                if (col.kind != L.kind || col.width != L.width)
+                    return fail(a, NGZ_E_LIMIT, "added columns of one IE that differ in kind or width");
+            }
+            sl.width = L.width;
+            n.sel_scratch[n.rp.n_sel] = true;
+            n.sel_off[n.rp.n_sel] = enr_need;
+            enr_need += al((uint64_t)L.width * (((uint64_t)si.n_records + 3) & ~3ull));
+        }
+        if (L.kind == NGZ_K_VLEN) (is_value ? plans[s].val_ext : plans[s].key_ext) |= 1u << index;
+        ++n.rp.n_sel;
+        return NGZ_OK;
     }
-    // dictionaries as they were: a failed push puts them back
-    const std::vector<int64_t> keep_t = a->templates, keep_p = a->ports, keep_d = a->domains;
-    const std::vector<int> keep_vw = a->val_w, keep_kw = a->key_w, keep_kk = a->key_kind_seen, keep_vk = a->val_kind_seen;
-    bool gc_done = false;
-    auto restore = [&]() {
-        if (new_peer) {
-            a->peers.pop_back();
-            a->peer_time.pop_back();
-            a->peer_index.erase(pk);
-            new_peer = false;
+
+    // per-slot plans: FieldRef lookup (IE, occurrence among non-scope fields), types fixed at first sight
+    int build_slot_plans(ngz_ctx *ctx, ngz_enrich *e) {
+        plans.resize(std::max<uint32_t>(S, 1));
+        if (enr) {
+            writer = ngz_enrich_writer_id(e);
+            ngz_enrich_value_arena(e, &enr_arena, nullptr, nullptr);
         }
-        a->templates = keep_t;
-        a->ports = keep_p;
-        a->domains = keep_d;
-        a->val_w = keep_vw;
-        a->key_w = keep_kw;
-        a->key_kind_seen = keep_kk;
-        a->val_kind_seen = keep_vk;
-    };
-    auto put = [&](std::vector<int64_t> &d, int64_t x, uint32_t cap, int &bit) -> int {
-        bit = dict_put(d, x, cap);
-        if (bit < 0 && !gc_done) {  // full: free the entries no live group uses, then retry
-            const int r = dict_gc(a);
-            if (r) return r;
-            gc_done = true;
-            bit = dict_put(d, x, cap);
+        enr_need = al(writer.size() + 1);
+        for (s = 0; s < S; ++s) {
+            AggSlotPlan &sp = plans[s];
+            memset(&sp, 0, sizeof sp);
+            const ngz_slot_info &si = out->slots[s];
+            sp.proto = si.proto;
+            sp.bytes = ctx->last_in.bytes;
+            const ngze::SlotResult *er = enr && s < enr->size() ? &(*enr)[s] : nullptr;
+            if (er && er->dropped) {  // records with scope fields are no items (actor.rs:178, :237)
+                sp.dropped = 1;
+                continue;
+            }
+            if (!si.n_records || !si.columns) continue;
+            nf = ngz_slot_fields(ctx, s, nullptr, 0);
+            if (nf < 0) return undo.refuse(NGZ_E_INVALID, "ngz_slot_fields");
+            fi.resize(std::max(nf, 1));
+            ngz_slot_fields(ctx, s, fi.data(), (uint32_t)nf);
+            if (er) {
+                if (er->rows != si.n_records || er->cols.size() > NGZ_AGG_ENRICH_MAX_COLUMNS)
+                    return undo.refuse(NGZ_E_INVALID, "the enricher's results do not match the batch");
+                sfields.resize(std::max(nf, 1));
+                for (int i = 0; i < nf; ++i) sfields[i] = ngz_agg_slot_field{fi[i].pen, fi[i].ie_id, (uint8_t)(fi[i].is_scope ? 1 : 0), 0};
+                srefs.resize(std::max<size_t>(er->cols.size(), 1));
+                for (size_t c = 0; c < er->cols.size(); ++c) srefs[c] = ngz_agg_ref{er->cols[c].pen, er->cols[c].ie_id, er->cols[c].index};
+            }
+            own_keys = own_vals = 0;
+            int tbit;
+            if (int r = put(a->templates, ((int64_t)si.proto << 16) | si.template_id, SET_BITS, tbit)) return undo.refuse(r, a->last_error);
+            if (tbit < 0) return undo.refuse(NGZ_AGG_E_OVERFLOW, "more than 64 template ids in live windows");
+            sp.tpl_bit = 1ull << tbit;
+            for (uint32_t i = 0; i < a->P.n_keys + a->P.n_vals; ++i) {  // the keys, then the aggregated fields
+                const bool is_value = i >= a->P.n_keys;
+                const uint32_t index = is_value ? i - a->P.n_keys : i;
+                const ngz_agg_field &f = is_value ? a->vals[index] : a->keys[index];
+                Loc L;
+                if (!er) locate_own(si, fi.data(), nf, f, L);
+                else if (int r = locate_enriched(f, is_value, index, L)) return undo.refuse(r, a->last_error);
+                if (!L.found) continue;
+                if (const char *why = is_value ? accept_value(a, sp, index, L) : accept_key(a, sp, index, L))
+                    return undo.refuse(NGZ_E_LIMIT, why);
+            }
+            sp.usable = 1;
+            if (!enr_slots.empty() && enr_slots.back().slot == s) {  // the fields on own columns are present in every row
+                ngza::ResolvePlan &rp = enr_slots.back().rp;
+                rp.own_keys = own_keys;
+                rp.own_vals = own_vals;
+                sp.xbytes = enr_arena;
+            }
         }
         return NGZ_OK;
-    };
-    int port_bit;
-    if (int r = put(a->ports, peer_port, SET_BITS, port_bit)) { restore(); return r; }
-    if (port_bit < 0) { restore(); return fail(a, NGZ_AGG_E_OVERFLOW, "more than 64 peer ports in live windows"); }
-    // per-slot plans: FieldRef lookup (IE, occurrence among non-scope fields), types fixed at first sight
-    const uint32_t S = out->n_slots;
-    std::vector<AggSlotPlan> plans(std::max<uint32_t>(S, 1));
-    std::vector<ngz_field_info> fi;
-    // enriched push: the slots with a resolve pass, and what of the aggregator's scratch they use
-    // (offsets into enr_buf until it is sized; the writer id sits at its start)
-    struct EnrSlot {
-        uint32_t slot;
-        ngza::ResolvePlan rp;
-        uint64_t kpres_off, vpres_off;
-        bool sel_scratch[ngza::RS_MAX_SEL];  // the field has a resolved column, at sel_off
-        uint64_t sel_off[ngza::RS_MAX_SEL];
-    };
-    struct EnrFix {  // a plan column in the scratch
-        uint32_t slot, index;
-        bool is_value;
-        uint64_t off;
-    };
-    std::vector<EnrSlot> enr_slots;
-    std::vector<EnrFix> enr_fix;
-    const std::string writer = enr ? std::string(ngz_enrich_writer_id(e)) : std::string();
-    auto al256 = [](uint64_t x) { return (x + 255) & ~255ull; };
-    uint64_t enr_need = al256(writer.size() + 1);
-    const uint8_t *enr_arena = nullptr;
-    if (enr) ngz_enrich_value_arena(e, &enr_arena, nullptr, nullptr);
-    std::vector<ngz_agg_slot_field> sfields;
-    std::vector<ngz_agg_ref> srefs;
-    for (uint32_t s = 0; s < S; ++s) {
-        AggSlotPlan &sp = plans[s];
-        memset(&sp, 0, sizeof sp);
-        const ngz_slot_info &si = out->slots[s];
-        sp.proto = si.proto;
-        sp.bytes = ctx->last_in.bytes;
-        const ngze::SlotResult *er = enr && s < enr->size() ? &(*enr)[s] : nullptr;
-        if (er && er->dropped) {  // records with scope fields are no items (actor.rs:178, :237)
-            sp.dropped = 1;
-            continue;
-        }
-        if (!si.n_records || !si.columns) continue;
-        const int nf = ngz_slot_fields(ctx, s, nullptr, 0);
-        if (nf < 0) { restore(); return fail(a, NGZ_E_INVALID, "ngz_slot_fields"); }
-        fi.resize(std::max(nf, 1));
-        ngz_slot_fields(ctx, s, fi.data(), (uint32_t)nf);
-        if (er) {
-            if (er->rows != si.n_records || er->cols.size() > NGZ_AGG_ENRICH_MAX_COLUMNS) {
-                restore();
-                return fail(a, NGZ_E_INVALID, "the enricher's results do not match the batch");
-            }
-            sfields.resize(std::max(nf, 1));
-            for (int i = 0; i < nf; ++i) sfields[i] = ngz_agg_slot_field{fi[i].pen, fi[i].ie_id, (uint8_t)(fi[i].is_scope ? 1 : 0), 0};
-            srefs.resize(std::max<size_t>(er->cols.size(), 1));
-            for (size_t c = 0; c < er->cols.size(); ++c) srefs[c] = ngz_agg_ref{er->cols[c].pen, er->cols[c].ie_id, er->cols[c].index};
-        }
-        int es = -1;  // the slot's entry of enr_slots, once a field needs the resolve pass
-        uint32_t own_keys = 0, own_vals = 0;  // enriched push: the selected fields on the template's own columns
-        // Where a selected field's column is: the template's own (ngz_agg_push), or with the
-        // enrichment an added column read in place, or a resolved column of the scratch
-        struct Loc {
-            bool found = false;
-            uint8_t kind = 0;
-            uint32_t width = 0;
-            const uint8_t *col = nullptr;
-            bool scratch = false;
-        };
-        auto locate = [&](const ngz_agg_field &f, bool is_value, uint32_t index, Loc &L) -> int {
-            if (!er) {
-                uint32_t seen = 0;
-                for (int i = 0; i < nf; ++i) {
-                    if (fi[i].is_scope) continue;
-                    if (fi[i].pen == f.pen && fi[i].ie_id == f.ie_id) {
-                        if (seen == f.index) {
-                            L = Loc{true, fi[i].kind, fi[i].width, si.columns + (uint64_t)si.capacity * fi[i].col_off, false};
-                            return NGZ_OK;
-                        }
-                        ++seen;
-                    }
-                }
-                return NGZ_OK;
-            }
-            ngz_agg_enrich_resolution res;
-            if (ngza::resolve_field(sfields.data(), (uint32_t)nf, srefs.data(), (uint32_t)er->cols.size(), f.pen, f.ie_id,
-                                    f.index, &res))
-                return fail(a, NGZ_E_LIMIT, "more added columns than the aggregation takes");
-            if (res.kind == NGZ_AGG_RES_NONE) return NGZ_OK;
-            if (res.kind == NGZ_AGG_RES_OWN) {
-                const ngz_field_info &o = fi[res.own_field];
-                L = Loc{true, o.kind, o.width, si.columns + (uint64_t)si.capacity * o.col_off, false};
-                (is_value ? own_vals : own_keys) |= 1u << index;
-                return NGZ_OK;
-            }
-            if (es < 0) {
-                es = (int)enr_slots.size();
-                enr_slots.emplace_back();
-                EnrSlot &n = enr_slots.back();
-                memset(&n, 0, sizeof n);
-                n.slot = s;
-                n.rp.mask = er->mask;
-                n.rp.n_rows = si.n_records;
-                for (size_t c = 0; c < er->cols.size(); ++c) n.rp.col[c] = er->cols[c].data;
-                n.kpres_off = enr_need;
-                enr_need += al256(4ull * si.n_records);
-                n.vpres_off = enr_need;
-                enr_need += al256(4ull * si.n_records);
-            }
-            EnrSlot &n = enr_slots[es];
-            ngza::ResolveSel &sl = n.rp.sel[n.rp.n_sel];
-            sl.bit = (uint8_t)index;
-            sl.is_value = is_value ? 1 : 0;
-            sl.ordinal = res.ordinal;
-            sl.writer_after = res.kind == NGZ_AGG_RES_WRITER || res.writer_after;
-            sl.wid_len = (uint32_t)writer.size();
-            for (uint32_t c = 0; c < res.n_candidates; ++c) sl.cand |= 1u << res.candidates[c];
-            L.found = true;
-            if (res.kind == NGZ_AGG_RES_ADDED && res.n_candidates == 1 && !res.writer_after) {
-                const ngz_enrich_column &c = er->cols[res.candidates[0]];  // read in place
-                L.kind = c.kind;
-                L.width = c.width;
-                L.col = c.data;
-            } else {  // several candidates or the writer id: the chosen cell in a resolved column
-                L.kind = NGZ_K_VLEN;
-                L.width = 16;
-                for (uint32_t c = 0; c < res.n_candidates; ++c) {
-                    const ngz_enrich_column &col = er->cols[res.candidates[c]];
-                    if (c == 0 && !sl.writer_after) {
-                        L.kind = col.kind;
-                        L.width = col.width;
-                    }
-                    if (col.kind != L.kind || col.width != L.width)
-                        return fail(a, NGZ_E_LIMIT, "added columns of one IE that differ in kind or width");
-                }
-                sl.width = L.width;
-                n.sel_scratch[n.rp.n_sel] = true;
-                n.sel_off[n.rp.n_sel] = enr_need;
-                enr_fix.push_back(EnrFix{s, index, is_value, enr_need});
-                enr_need += al256((uint64_t)L.width * (((uint64_t)si.n_records + 3) & ~3ull));
-                L.scratch = true;  // the column's address follows once the scratch is sized (enr_fix)
-            }
-            if (L.kind == NGZ_K_VLEN) (is_value ? sp.val_ext : sp.key_ext) |= 1u << index;
-            ++n.rp.n_sel;
-            return NGZ_OK;
-        };
-        int tbit;
-        if (int r = put(a->templates, ((int64_t)si.proto << 16) | si.template_id, SET_BITS, tbit)) { restore(); return r; }
-        if (tbit < 0) { restore(); return fail(a, NGZ_AGG_E_OVERFLOW, "more than 64 template ids in live windows"); }
-        sp.tpl_bit = 1ull << tbit;
-        for (uint32_t k = 0; k < a->P.n_keys; ++k) {
-            Loc f;
-            if (int r = locate(a->keys[k], false, k, f)) { restore(); return r; }
-            if (!f.found) continue;
-            if (a->P.key_kind[k] == KK_BYTES) {
-                // any length, fixed or variable-length (a record's text / bytes, BVAL)
-                if (f.kind == NGZ_K_FAIL) { restore(); return fail(a, NGZ_E_LIMIT, "key field of a failing template"); }
-                if (f.kind == NGZ_K_VLEN) sp.key_vlen |= 1u << k;
-                sp.key_col[k] = f.col;
-                sp.key_w[k] = f.width;
-                if (a->key_w[k] < 0) a->key_w[k] = f.width;
-                if (a->key_kind_seen[k] < 0) a->key_kind_seen[k] = f.kind;
-                continue;
-            }
-            if (f.kind == NGZ_K_VLEN || f.kind == NGZ_K_FAIL) {
-                restore();
-                return fail(a, NGZ_E_LIMIT, "fixed-size key field sent variable-length (its records fail to decode)");
-            }
-            if (f.width > a->P.key_slot[k]) { restore(); return fail(a, NGZ_E_LIMIT, "key field wider than its row slot"); }
-            if (a->P.packed && f.width != a->P.key_pw[k]) {
-                restore();
-                return fail(a, NGZ_E_LIMIT, "key column width differs from the IE's width");
-            }
-            sp.key_col[k] = f.col;
-            sp.key_w[k] = f.width;
-            if (a->key_w[k] < 0) a->key_w[k] = f.width;
-            if (a->key_kind_seen[k] < 0) a->key_kind_seen[k] = f.kind;
-        }
-        for (uint32_t v = 0; v < a->P.n_vals; ++v) {
-            Loc f;
-            if (int r = locate(a->vals[v], true, v, f)) { restore(); return r; }
-            if (!f.found) continue;
-            const int vc = a->P.val_vc[v];
-            if ((vc == VC_VBYTES || vc == VC_VLIST) && f.kind != NGZ_K_FAIL) {
-                // Box<[u8]> values: any length, fixed or variable-length (BVAL)
-                if (f.kind == NGZ_K_VLEN) sp.val_vlen |= 1u << v;
-                if (a->val_w[v] < 0) a->val_w[v] = f.width;
-                if (a->val_kind_seen[v] < 0) a->val_kind_seen[v] = f.kind;
-                sp.val_col[v] = f.col;
-                sp.val_w[v] = f.width;
-                continue;
-            }
-            if (f.kind == NGZ_K_VLEN || f.kind == NGZ_K_FAIL || (vc == VC_BYTES && f.width > 32)) {
-                restore();
-                return fail(a, NGZ_E_LIMIT, "fixed-size aggregated field sent variable-length (its records fail to decode)");
-            }
-            const bool int_like = vc == VC_UINT || vc == VC_SINT || vc == VC_RANK;
-            if ((int_like && f.width != 1 && f.width != 2 && f.width != 4 && f.width != 8) ||
-                (vc == VC_F32 && f.width != 4) || (vc == VC_F64 && f.width != 8) || (vc == VC_IPV6 && f.width != 16) ||
-                (vc == VC_DTFRAC && f.width != 8)) {
-                restore();
-                return fail(a, NGZ_E_LIMIT, "aggregated field of an unexpected column width");
-            }
-            if (a->val_w[v] >= 0 && a->val_w[v] != f.width) {
-                restore();
-                return fail(a, NGZ_E_LIMIT, "aggregated field width differs between templates");
-            }
-            a->val_w[v] = f.width;
-            if (a->val_kind_seen[v] < 0) a->val_kind_seen[v] = f.kind;
-            sp.val_col[v] = f.col;
-            sp.val_w[v] = f.width;
-        }
-        sp.usable = 1;
-        if (es >= 0) {  // the fields on own columns are present in every row
-            ngza::ResolvePlan &rp = enr_slots[es].rp;
-            rp.own_keys = own_keys;
-            rp.own_vals = own_vals;
-            sp.xbytes = enr_arena;
-        }
     }
-    const uint32_t D = out->n_dgrams, NS = out->n_sets;
-    if (!D || !NS) return NGZ_OK;
-    const bool enr_rows = !enr_slots.empty();  // some selected field is per row: the ENR kernels, the general path
-    if (enr_rows) {
-        // the aggregator's scratch for this push: the writer id, the presence words, the resolved columns
-        if (enr_need > a->enr_cap) {
-            hipFree(a->enr_buf);
-            a->enr_buf = nullptr;
-            a->enr_cap = 0;
-            if (hipMalloc(&a->enr_buf, enr_need) != hipSuccess) { restore(); return fail(a, NGZ_E_NOMEM, "enrichment scratch"); }
-            a->enr_cap = enr_need;
-        }
+
+    // The enrichment scratch, the passes up to the one synchronisation every push has (the record count
+    // sizes the record kernels, new domains need entries), the new domains, the per-record buffers
+    int prologue(int64_t collection_time_ms) {
+        // an enriched push with per-row fields: the writer id, the presence words, the resolved columns
+        enr_rows = !enr_slots.empty();
+        if (enr_rows && !grow(a->enr_buf, a->enr_cap, enr_need)) return undo.refuse(NGZ_E_NOMEM, "enrichment scratch");
         for (EnrSlot &n : enr_slots) {
             n.rp.kpres = (uint32_t *)(a->enr_buf + n.kpres_off);
             n.rp.vpres = (uint32_t *)(a->enr_buf + n.vpres_off);
-            for (uint32_t i = 0; i < n.rp.n_sel; ++i)
-                if (n.sel_scratch[i]) n.rp.sel[i].resolved = a->enr_buf + n.sel_off[i];
             AggSlotPlan &sp = plans[n.slot];
+            for (uint32_t i = 0; i < n.rp.n_sel; ++i) {
+                ngza::ResolveSel &sl = n.rp.sel[i];
+                if (!n.sel_scratch[i]) continue;
+                sl.resolved = a->enr_buf + n.sel_off[i];
+                (sl.is_value ? sp.val_col : sp.key_col)[sl.bit] = sl.resolved;
+            }
             sp.kpres = n.rp.kpres;
             sp.vpres = n.rp.vpres;
             sp.wid = a->enr_buf;
         }
-        for (const EnrFix &f : enr_fix) (f.is_value ? plans[f.slot].val_col : plans[f.slot].key_col)[f.index] = a->enr_buf + f.off;
-    }
-    // scratch: has_rec[D], ts[D], pm[D], dginfo[D], cnt/rstart[NS+1], cub temp
-    size_t cub_max = 0, cub_sum = 0;
-    hipcub::DeviceScan::InclusiveScan(nullptr, cub_max, (uint32_t *)nullptr, (uint32_t *)nullptr, hipcub::Max(), D,
-                                      a->stream);
-    hipcub::DeviceScan::ExclusiveSum(nullptr, cub_sum, (uint32_t *)nullptr, (uint32_t *)nullptr, NS + 1, a->stream);
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t o_has = 0, o_ts = o_has + al(4ull * D), o_pm = o_ts + al(4ull * D), o_dg = o_pm + al(4ull * D),
-                 o_cnt = o_dg + al(2ull * D), o_rs = o_cnt + al(4ull * (NS + 1)), o_cub = o_rs + al(4ull * (NS + 1)),
-                 need = o_cub + al(std::max(cub_max, cub_sum));
-    if (need > a->scratch_cap) {
-        hipFree(a->scratch);
-        a->scratch = nullptr;
-        if (hipMalloc(&a->scratch, need) != hipSuccess) { a->scratch_cap = 0; restore(); return fail(a, NGZ_E_NOMEM, "scratch"); }
-        a->scratch_cap = need;
-    }
-    uint8_t *sc = (uint8_t *)a->scratch;
-    uint32_t *has_rec = (uint32_t *)(sc + o_has), *ts = (uint32_t *)(sc + o_ts), *pm = (uint32_t *)(sc + o_pm);
-    uint16_t *dginfo = (uint16_t *)(sc + o_dg);
-    uint32_t *cnt = (uint32_t *)(sc + o_cnt), *rstart = (uint32_t *)(sc + o_rs);
-    void *cub_tmp = sc + o_cub;
-    if (S > a->plans_cap) {
-        hipFree(a->plans);
-        a->plans = nullptr;
-        if (hipMalloc(&a->plans, sizeof(AggSlotPlan) * S) != hipSuccess) {
-            a->plans_cap = 0;
-            restore();
-            return fail(a, NGZ_E_NOMEM, "plans");
+        // scratch: has_rec[D], ts[D], pm[D], dginfo[D], cnt/rstart[NS+1], cub temp
+        size_t cub_max = 0, cub_sum = 0;
+        hipcub::DeviceScan::InclusiveScan(nullptr, cub_max, (uint32_t *)nullptr, (uint32_t *)nullptr, hipcub::Max(), D,
+                                          a->stream);
+        hipcub::DeviceScan::ExclusiveSum(nullptr, cub_sum, (uint32_t *)nullptr, (uint32_t *)nullptr, NS + 1, a->stream);
+        const size_t o_has = 0, o_ts = o_has + al(4ull * D), o_pm = o_ts + al(4ull * D), o_dg = o_pm + al(4ull * D),
+                     o_cnt = o_dg + al(2ull * D), o_rs = o_cnt + al(4ull * (NS + 1)), o_cub = o_rs + al(4ull * (NS + 1)),
+                     need = o_cub + al(std::max(cub_max, cub_sum));
+        if (!grow(a->scratch, a->scratch_cap, need)) return undo.refuse(NGZ_E_NOMEM, "scratch");
+        uint8_t *sc = a->scratch;
+        uint32_t *has_rec = (uint32_t *)(sc + o_has), *ts = (uint32_t *)(sc + o_ts), *cnt = (uint32_t *)(sc + o_cnt);
+        pm = (uint32_t *)(sc + o_pm);
+        dginfo = (uint16_t *)(sc + o_dg);
+        rstart = (uint32_t *)(sc + o_rs);
+        void *cub_tmp = sc + o_cub;
+        if (!grow(a->plans, a->plans_cap, S)) return undo.refuse(NGZ_E_NOMEM, "plans");
+        AGG_HIP(a, hipMemcpyAsync(a->plans, plans.data(), sizeof(AggSlotPlan) * S, hipMemcpyHostToDevice, st));
+        P = a->P;
+        P.push_id = ++a->push_id;
+        P.port_bit = (uint32_t)port_bit;
+        P.peer = pi;
+        P.coll_flip = (uint64_t)collection_time_ms ^ (1ull << 63);
+        // owner path only where groups get few records per push (many groups per record): with
+        // few, hot groups the wave / workgroup pre-aggregation of k_agg_apply serves them better
+        // and the owner stores and checks would only add traffic.  Decided from the groups held
+        // before the push (an empty table: the first push of any key).
+        P.own = P.own && a->opt_owner && (a->live == 0 || a->live * 8 > (uint64_t)out->n_records);
+        AGG_HIP(a, hipEventRecord(a->ev0, st));
+        AGG_HIP(a, hipMemsetAsync(has_rec, 0, 4ull * D, st));
+        AGG_HIP(a, hipMemsetAsync(a->late, 0, 8, st));
+        AGG_HIP(a, hipMemsetAsync(a->err, 0, 4, st));
+        AGG_HIP(a, hipMemsetAsync(a->newdom, 0, NEWDOM_SLOTS * 8, st));
+        AGG_HIP(a, hipMemsetAsync(a->n_claims, 0, 8, st));
+        if (enr_rows) {
+            // resolve pass: one launch per slot in which a selected field lands past the template's own columns
+            if (!writer.empty())
+                AGG_HIP(a, hipMemcpyAsync(a->enr_buf, writer.data(), writer.size(), hipMemcpyHostToDevice, st));
+            AGG_HIP(a, hipEventRecord(a->ev_r0, st));
+            for (const EnrSlot &n : enr_slots)
+                if (ngza::resolve_launch(n.rp, st)) return undo.refuse(NGZ_E_DEVICE, "resolve pass launch");
+            AGG_HIP(a, hipEventRecord(a->ev_r1, st));
         }
-        a->plans_cap = S;
-    }
-    hipStream_t st = a->stream;
-    AGG_HIP(a, hipMemcpyAsync(a->plans, plans.data(), sizeof(AggSlotPlan) * S, hipMemcpyHostToDevice, st));
-    AggParams P = a->P;
-    P.push_id = ++a->push_id;
-    P.port_bit = (uint32_t)port_bit;
-    P.peer = pi;
-    P.coll_flip = (uint64_t)collection_time_ms ^ (1ull << 63);
-    // owner path only where groups get few records per push (many groups per record): with
-    // few, hot groups the wave / workgroup pre-aggregation of k_agg_apply serves them better
-    // and the owner stores and checks would only add traffic.  Decided from the groups held
-    // before the push (an empty table: the first push of any key).
-    P.own = P.own && a->opt_owner && (a->live == 0 || a->live * 8 > (uint64_t)out->n_records);
-    AGG_HIP(a, hipEventRecord(a->ev0, st));
-    AGG_HIP(a, hipMemsetAsync(has_rec, 0, 4ull * D, st));
-    AGG_HIP(a, hipMemsetAsync(a->late, 0, 8, st));
-    AGG_HIP(a, hipMemsetAsync(a->err, 0, 4, st));
-    AGG_HIP(a, hipMemsetAsync(a->newdom, 0, NEWDOM_SLOTS * 8, st));
-    AGG_HIP(a, hipMemsetAsync(a->n_claims, 0, 8, st));
-    const ngz_dgram_hdr *hdr = out->dgrams;
-    const ngz_set_info *sets = out->sets;
-    if (enr_rows) {
-        // resolve pass: one launch per slot in which a selected field lands past the template's own columns
-        if (!writer.empty())
-            AGG_HIP(a, hipMemcpyAsync(a->enr_buf, writer.data(), writer.size(), hipMemcpyHostToDevice, st));
-        AGG_HIP(a, hipEventRecord(a->ev_r0, st));
-        for (const EnrSlot &n : enr_slots)
-            if (ngza::resolve_launch(n.rp, st)) { restore(); return fail(a, NGZ_E_DEVICE, "resolve pass launch"); }
-        AGG_HIP(a, hipEventRecord(a->ev_r1, st));
-    }
-    if (enr)
-        hipLaunchKernelGGL(k_agg_dgram_kept, dim3(grid_for(NS)), dim3(256), 0, st, sets, NS, D, a->plans, S, has_rec);
-    else
-        hipLaunchKernelGGL(k_agg_dgram, dim3(grid_for(NS)), dim3(256), 0, st, sets, NS, D, has_rec);
-    hipLaunchKernelGGL(k_agg_ts, dim3(grid_for(D)), dim3(256), 0, st, hdr, has_rec, D, ts);
-    size_t tmp = cub_max;
-    AGG_HIP(a, hipcub::DeviceScan::InclusiveScan(cub_tmp, tmp, ts, pm, hipcub::Max(), D, st));
-    hipLaunchKernelGGL(k_agg_late, dim3(grid_for(D)), dim3(256), 0, st, hdr, has_rec, pm, D, a->peer_time[pi],
-                       a->lateness_ms, a->dom_dict, dginfo, a->newdom, a->err);
-    // record starts of every set: n copied out of the set table (stride 16 B) then scanned
-    AGG_HIP(a, hipMemsetAsync(cnt + NS, 0, 4, st));
-    AGG_HIP(a, hipMemcpy2DAsync(cnt, 4, (const uint8_t *)sets + offsetof(ngz_set_info, n), sizeof(ngz_set_info), 4, NS,
-                                hipMemcpyDeviceToDevice, st));
-    tmp = cub_sum;
-    AGG_HIP(a, hipcub::DeviceScan::ExclusiveSum(cub_tmp, tmp, cnt, rstart, NS + 1, st));
-    // one synchronisation: the record count sizes the record kernels, new domains need entries
-    uint32_t n_rec = 0;
-    unsigned long long newdom[NEWDOM_SLOTS];
-    unsigned int errv = 0;
-    AGG_HIP(a, hipMemcpyAsync(&n_rec, rstart + NS, 4, hipMemcpyDeviceToHost, st));
-    AGG_HIP(a, hipMemcpyAsync(newdom, a->newdom, sizeof newdom, hipMemcpyDeviceToHost, st));
-    AGG_HIP(a, hipMemcpyAsync(&errv, a->err, 4, hipMemcpyDeviceToHost, st));
-    AGG_HIP(a, hipStreamSynchronize(st));
-    if (errv & 1) { restore(); return fail(a, NGZ_AGG_E_OVERFLOW, "more than 256 new observation domains in one push"); }
-    bool fix = false;
-    for (uint32_t i = 0; i < NEWDOM_SLOTS; ++i) {
-        if (!newdom[i]) continue;
-        int bit;
-        if (int r = put(a->domains, (int64_t)(uint32_t)newdom[i], DOM_SLOTS, bit)) { restore(); return r; }
-        if (bit < 0) {
-            restore();
-            upload_domains(a);
-            return fail(a, NGZ_AGG_E_OVERFLOW, "more than 128 observation domains in live windows");
+        if (enr)
+            hipLaunchKernelGGL(k_agg_dgram_kept, dim3(grid_for(NS)), dim3(256), 0, st, out->sets, NS, D, a->plans, S, has_rec);
+        else
+            hipLaunchKernelGGL(k_agg_dgram, dim3(grid_for(NS)), dim3(256), 0, st, out->sets, NS, D, has_rec);
+        hipLaunchKernelGGL(k_agg_ts, dim3(grid_for(D)), dim3(256), 0, st, out->dgrams, has_rec, D, ts);
+        size_t tmp = cub_max;
+        AGG_HIP(a, hipcub::DeviceScan::InclusiveScan(cub_tmp, tmp, ts, pm, hipcub::Max(), D, st));
+        hipLaunchKernelGGL(k_agg_late, dim3(grid_for(D)), dim3(256), 0, st, out->dgrams, has_rec, pm, D, a->peer_time[pi],
+                           a->lateness_ms, a->dom_dict, dginfo, a->newdom, a->err);
+        // record starts of every set: n copied out of the set table (stride 16 B) then scanned
+        const ngz_set_info *sets = out->sets;
+        AGG_HIP(a, hipMemsetAsync(cnt + NS, 0, 4, st));
+        AGG_HIP(a, hipMemcpy2DAsync(cnt, 4, (const uint8_t *)sets + offsetof(ngz_set_info, n), sizeof(ngz_set_info), 4, NS,
+                                    hipMemcpyDeviceToDevice, st));
+        tmp = cub_sum;
+        AGG_HIP(a, hipcub::DeviceScan::ExclusiveSum(cub_tmp, tmp, cnt, rstart, NS + 1, st));
+        unsigned long long newdom[NEWDOM_SLOTS];
+        AGG_HIP(a, hipMemcpyAsync(&n_rec, rstart + NS, 4, hipMemcpyDeviceToHost, st));
+        AGG_HIP(a, hipMemcpyAsync(newdom, a->newdom, sizeof newdom, hipMemcpyDeviceToHost, st));
+        AGG_HIP(a, hipMemcpyAsync(&errv, a->err, 4, hipMemcpyDeviceToHost, st));
+        AGG_HIP(a, hipStreamSynchronize(st));
+        if (errv & 1) return undo.refuse(NGZ_AGG_E_OVERFLOW, "more than 256 new observation domains in one push");
+        bool fix = false;
+        for (uint32_t i = 0; i < NEWDOM_SLOTS; ++i) {
+            if (!newdom[i]) continue;
+            int bit;
+            if (int r = put(a->domains, (int64_t)(uint32_t)newdom[i], DOM_SLOTS, bit)) return undo.refuse(r, a->last_error);
+            if (bit < 0) {
+                undo.stage = PushUndo::domains;
+                return undo.refuse(NGZ_AGG_E_OVERFLOW, "more than 128 observation domains in live windows");
+            }
+            fix = true;
         }
-        fix = true;
+        if (fix) {
+            if (int r = upload_domains(a)) return undo.refuse(r, a->last_error);
+            hipLaunchKernelGGL(k_agg_domfix, dim3(grid_for(D)), dim3(256), 0, st, out->dgrams, a->dom_dict, dginfo, D, a->err);
+        }
+        undo.stage = PushUndo::domains;  // the device's dictionary may hold the new domains: a refusal uploads it again
+        // per-record buffers: contexts (16 B), rec_g, claims, two record lists, sort keys / values (x2)
+        R4 = al(4ull * std::max<uint32_t>(n_rec, 1));
+        for (uint32_t v = 0; v < P.n_vals; ++v) ordered = ordered || vc_ordered(P.val_vc[v]);
+        if (ordered)
+            hipcub::DeviceRadixSort::SortPairs(nullptr, sort_tmp, (uint32_t *)nullptr, (uint32_t *)nullptr,
+                                               (uint32_t *)nullptr, (uint32_t *)nullptr, (int)std::max<uint32_t>(n_rec, 1),
+                                               0, 32, st);
+        n_blk = ((uint64_t)n_rec + 255) / 256;
+        B0 = al(16ull * NS) + al(4 * (n_blk + 1));  // set contexts, block sets
+        if (!grow(a->rec_buf, a->rec_cap, B0 + 4 * R4 + (ordered ? 4 * R4 + al(sort_tmp) : 0)))
+            return undo.refuse(NGZ_E_NOMEM, "record buffers");
+        sctx = (uint4 *)a->rec_buf;
+        bset = (uint32_t *)(a->rec_buf + al(16ull * NS));
+        rec_g = (uint32_t *)(a->rec_buf + B0), claims = (uint32_t *)(a->rec_buf + B0 + R4);
+        list_a = (uint32_t *)(a->rec_buf + B0 + 2 * R4), list_b = (uint32_t *)(a->rec_buf + B0 + 3 * R4);
+        C = RecCtx{sctx, rstart, bset, NS, (uint64_t)n_rec, a->plans};
+        const uint32_t blocks = (uint32_t)((n_rec + 255) / 256);
+        static const uint32_t grid_cap = (uint32_t)std::max<int64_t>(1, ngz_knob("NGZ_AGG_GRID", 4096));
+        ig = std::max<uint32_t>(1, std::min<uint32_t>(blocks, grid_cap));
+        // claim / check keep no state across tiles: one record per thread, all of them in flight
+        fg = std::max<uint32_t>(1, std::min<uint32_t>(blocks, 1u << 20));
+        return NGZ_OK;
     }
-    if (fix) {
-        if (int r = upload_domains(a)) { restore(); return r; }
-        hipLaunchKernelGGL(k_agg_domfix, dim3(grid_for(D)), dim3(256), 0, st, hdr, a->dom_dict, dginfo, D, a->err);
-    }
-    // per-record buffers: contexts (16 B), rec_g, claims, two record lists, sort keys / values (x2)
-    const uint64_t R4 = al(4ull * std::max<uint32_t>(n_rec, 1));
-    const bool ordered = [&] {
-        for (uint32_t v = 0; v < P.n_vals; ++v)
-            if (vc_ordered(P.val_vc[v])) return true;
-        return false;
-    }();
-    size_t sort_tmp = 0;
-    if (ordered)
-        hipcub::DeviceRadixSort::SortPairs(nullptr, sort_tmp, (uint32_t *)nullptr, (uint32_t *)nullptr,
-                                           (uint32_t *)nullptr, (uint32_t *)nullptr, (int)std::max<uint32_t>(n_rec, 1),
-                                           0, 32, st);
-    const uint64_t n_blk = ((uint64_t)n_rec + 255) / 256;
-    const size_t B0 = al(16ull * NS) + al(4 * (n_blk + 1));  // set contexts, block sets
-    const size_t rec_need = B0 + 4 * R4 + (ordered ? 4 * R4 + al(sort_tmp) : 0);
-    if (rec_need > a->rec_cap) {
-        hipFree(a->rec_buf);
-        a->rec_buf = nullptr;
-        a->rec_cap = 0;
-        if (hipMalloc(&a->rec_buf, rec_need) != hipSuccess) { restore(); upload_domains(a); return fail(a, NGZ_E_NOMEM, "record buffers"); }
-        a->rec_cap = rec_need;
-    }
-    uint4 *sctx = (uint4 *)a->rec_buf;
-    uint32_t *bset = (uint32_t *)(a->rec_buf + al(16ull * NS));
-    uint32_t *rec_g = (uint32_t *)(a->rec_buf + B0), *claims = (uint32_t *)(a->rec_buf + B0 + R4),
-             *list_a = (uint32_t *)(a->rec_buf + B0 + 2 * R4), *list_b = (uint32_t *)(a->rec_buf + B0 + 3 * R4);
-    const RecCtx C{sctx, rstart, bset, NS, (uint64_t)n_rec, a->plans};
-    const uint32_t blocks = (uint32_t)((n_rec + 255) / 256);
-    static const uint32_t grid_cap = (uint32_t)std::max<int64_t>(1, ngz_knob("NGZ_AGG_GRID", 4096));
-    const uint32_t ig = std::max<uint32_t>(1, std::min<uint32_t>(blocks, grid_cap));
-    unsigned long long n_claims = 0;
-    auto rollback = [&](int rc, const std::string &why) {
-        if (n_claims)
-            hipLaunchKernelGGL(k_agg_unclaim, dim3(grid_for(n_claims)), dim3(256), 0, st, a->tags, claims, (uint64_t)n_claims);
-        if (P.has_bytes)  // the released claims' key tails: the arena as after the last push
-            hipMemcpyAsync(a->arena_used, &a->arena_mark, 8, hipMemcpyHostToDevice, st);
-        restore();
-        upload_domains(a);
-        if (hipStreamSynchronize(st) != hipSuccess) a->poisoned = true;
-        return fail(a, rc, why);
-    };
+
     // Low-cardinality path (packed keys, no byte-wise / ordered values): k_agg_lc_part reduces
     // every record in one pass into per-wave partial groups, k_agg_lc_merge combines them
     // per tag, claims and applies.  A wave with more than LC_NK key tuples in one window
     // context, or more than LC_MAX_TAGS tags in the push, sends the push to the general
-    // path below, with nothing claimed or applied (NGZ_AGG_OPT_LOWCARD: 0 never, 1 at any size;
-    // default from 2^16 records).
-    const int lc_now = a->opt_lowcard;  // NGZ_AGG_OPT_LOWCARD
-    // a push that found too many key tuples sends the next 15 pushes of the aggregator
-    // straight to the general path (high-cardinality keys pay for one try in 16)
-    const bool lc_try = lc_now == 1 || (lc_now != 0 && n_rec >= (1u << 16) && (a->lc_skip == 0 || --a->lc_skip == 0));
-    if (n_rec && P.packed && P.lds_ok && P.n_vals <= (uint32_t)LC_MAXV && P.n_keys <= (uint32_t)LC_MAXK &&
-        !ordered && lc_try && !enr_rows) {
+    // path, with nothing claimed or applied (NGZ_AGG_OPT_LOWCARD: 0 never, 1 at any size;
+    // default from 2^16 records).  done: the push is reduced (else not taken, or given up: the general path).
+    int lowcard(bool &done) {
+        const int lc_now = a->opt_lowcard;  // NGZ_AGG_OPT_LOWCARD
+        // a push that found too many key tuples sends the next 15 pushes of the aggregator
+        // straight to the general path (high-cardinality keys pay for one try in 16)
+        const bool lc_try = lc_now == 1 || (lc_now != 0 && n_rec >= (1u << 16) && (a->lc_skip == 0 || --a->lc_skip == 0));
+        if (!(n_rec && P.packed && P.lds_ok && P.n_vals <= (uint32_t)LC_MAXV && P.n_keys <= (uint32_t)LC_MAXK &&
+              !ordered && lc_try && !enr_rows))
+            return NGZ_OK;
         // one-wave workgroups; the lane-private LDS cells of LC_NK tuples bound the residency
         // (160 KB per CU): a grid of that many workgroups, a multiple of the 8 XCDs
         const size_t lds = lc_lds_bytes(P.n_vals);
         const uint32_t per_cu = (uint32_t)std::max<size_t>(1, std::min<size_t>(16, (160u * 1024 - 1024) / (lds + 256)));
         const uint32_t rg = std::max<uint32_t>(8, std::min<uint32_t>(256 * per_cu, (NS + 7) & ~7u));
         const uint32_t cap = rg * LC_NK * 4;  // 4 window contexts per wave; more: the general path
-        if (cap > a->lc_cap || !a->lc_cnt) {
-            hipFree(a->lc);
-            a->lc = nullptr;
-            a->lc_cap = 0;
-            if (!a->lc_cnt && hipMalloc(&a->lc_cnt, 16) != hipSuccess) a->lc_cnt = nullptr;
-            // the waves' entries, then the merge workgroups' slices
-            if (!a->lc_cnt ||
-                hipMalloc(&a->lc, sizeof(LcEntry) * ((size_t)cap + LCM_BLOCKS * LC_MAX_TAGS)) != hipSuccess) {
-                a->lc = nullptr;
-                restore();
-                upload_domains(a);
-                return fail(a, NGZ_E_NOMEM, "low-cardinality buffers");
-            }
-            a->lc_cap = cap;
-        }
-        if (NS > a->lc_sets_cap) {
-            hipFree(a->lc_sets);
-            a->lc_sets_cap = 0;
-            if (hipMalloc(&a->lc_sets, sizeof(LcSet) * (size_t)NS) != hipSuccess) {
-                a->lc_sets = nullptr;
-                restore();
-                upload_domains(a);
-                return fail(a, NGZ_E_NOMEM, "low-cardinality set descriptors");
-            }
-            a->lc_sets_cap = NS;
-        }
+        if (!a->lc_cnt && hipMalloc(&a->lc_cnt, 16) != hipSuccess) a->lc_cnt = nullptr;
+        // the waves' entries, then the merge workgroups' slices
+        if (!a->lc_cnt || !grow(a->lc, a->lc_cap, (size_t)cap + LCM_BLOCKS * LC_MAX_TAGS))
+            return undo.refuse(NGZ_E_NOMEM, "low-cardinality buffers");
+        if (!grow(a->lc_sets, a->lc_sets_cap, NS)) return undo.refuse(NGZ_E_NOMEM, "low-cardinality set descriptors");
         uint32_t kb = 0;
         for (uint32_t k = 0; k < P.n_keys; ++k) kb += 1 + 8 * P.key_pw[k];
         AGG_HIP(a, hipMemsetAsync(a->lc_cnt, 0, 16, st));
-        hipLaunchKernelGGL(k_agg_lc_sets, dim3(grid_for(NS)), dim3(256), 0, st, sets, NS, hdr, dginfo, a->plans, D, S,
+        hipLaunchKernelGGL(k_agg_lc_sets, dim3(grid_for(NS)), dim3(256), 0, st, out->sets, NS, out->dgrams, dginfo, a->plans, D, S,
                            a->lc_sets, a->late, a->err);
         hipLaunchKernelGGL(k_agg_lc_part, dim3(rg), dim3(64), lds, st, a->lc_sets, NS, a->plans, P, kb, a->lc,
                            a->lc_cnt, cap, a->lc_cnt + 1);
         AGG_HIP(a, hipGetLastError());
         const uint64_t room = a->limit - std::min(a->live, a->limit);
+        undo.stage = PushUndo::claims;
         hipLaunchKernelGGL(k_agg_lc_merge, dim3(LCM_BLOCKS), dim3(LCM_THREADS), 0, st, a->lc, cap, a->lc + cap,
                            a->lc_cnt, P, a->tags, a->rows, room, claims, a->n_claims, a->err);
         AGG_HIP(a, hipGetLastError());
@@ -3908,93 +3876,108 @@ static int push_impl(ngz_agg *a, ngz_enrich *e, const std::vector<ngze::SlotResu
         AGG_HIP(a, hipMemcpyAsync(&n_claims, a->n_claims, 8, hipMemcpyDeviceToHost, st));
         AGG_HIP(a, hipMemcpyAsync(&errv, a->err, 4, hipMemcpyDeviceToHost, st));
         AGG_HIP(a, hipStreamSynchronize(st));
-        if (errv & 16) { a->poisoned = true; return rollback(NGZ_E_DEVICE, "set table entry out of range"); }
+        if (errv & 16) { a->poisoned = true; return undo.refuse(NGZ_E_DEVICE, "set table entry out of range"); }
         if (!lcc[1]) {
             // the merge released its claims when the push did not fit: nothing to undo
-            if (errv & 2) return rollback(NGZ_AGG_E_OVERFLOW, "group table full");
-            if (errv & 32) return rollback(NGZ_AGG_E_OVERFLOW, "more groups than the aggregator's capacity");
+            if (errv & 2) return undo.refuse(NGZ_AGG_E_OVERFLOW, "group table full");
+            if (errv & 32) return undo.refuse(NGZ_AGG_E_OVERFLOW, "more groups than the aggregator's capacity");
             a->last_path = "lowcard";
-            goto done;
+            done = true;
+            return NGZ_OK;
         }
         // too many key tuples / distinct tags: the general path from the start (nothing was
-        // claimed or applied; its claim pass counts the late records again)
+        // claimed or applied; its claim pass counts the late records again).  The stage stays `claims`,
+        // with no claim to release: only the arena refusal of claim() would notice, and packed keys have no tails
         AGG_HIP(a, hipMemsetAsync(a->late, 0, 8, st));
         a->lc_skip = 16;  // the next 15 pushes take the general path, the 16th tries this one again
+        return NGZ_OK;
     }
-    a->last_path = "general";
-    {
-    hipLaunchKernelGGL(k_agg_recinfo, dim3(grid_for(NS, 256, 4096)), dim3(256), 0, st, sets, NS, hdr, dginfo, a->plans, D,
-                       S, sctx, a->err);
-    if (n_blk) hipLaunchKernelGGL(k_agg_bset, dim3(grid_for(n_blk, 256, 4096)), dim3(256), 0, st, rstart, NS, n_blk, bset);
-    AGG_HIP(a, hipGetLastError());
-    if (P.has_bytes && n_rec) {
-        // byte values longer than 32 bytes: room in the arena for every tail this push can write.
-        // Key claims and ordered folds write at most one tail per group and field, and a push
-        // touches at most every slot of the table: the bound is the smaller of the records' tails
-        // and slots x byte fields x the longest tail (10^8 records of a 64-byte key over a few
-        // groups reserve 2 slots per group's worth, not 3 GB)
-        unsigned long long nd[2] = {0, 0};
-        AGG_HIP(a, hipMemsetAsync(a->arena_used + 1, 0, 16, st));
-        AGG_LAUNCH_ENR(k_agg_tail_need, dim3(grid_for(n_rec, 256, 4096)), dim3(256), 0, st, C, P, a->arena_used + 1);
-        AGG_HIP(a, hipMemcpyAsync(nd, a->arena_used + 1, 16, hipMemcpyDeviceToHost, st));
-        AGG_HIP(a, hipStreamSynchronize(st));
-        uint32_t n_bval = 0;
-        for (uint32_t k = 0; k < P.n_keys; ++k) n_bval += P.key_kind[k] == KK_BYTES;
-        for (uint32_t v = 0; v < P.n_vals; ++v) n_bval += P.val_vc[v] == VC_VBYTES || P.val_vc[v] == VC_VLIST;
-        const uint64_t need = std::min<uint64_t>(nd[0], a->slots * n_bval * nd[1]);
-        if (int r = arena_reserve(a, need)) { restore(); upload_domains(a); return r; }
-        P.arena = a->P.arena;
-        P.arena_cap = a->P.arena_cap;
-    }
-    // claim / check keep no state across tiles: one record per thread, all of them in flight
-    const uint32_t fg = std::max<uint32_t>(1, std::min<uint32_t>(blocks, 1u << 20));
-    if (n_rec) {
-        AGG_HIP(a, hipMemsetAsync(a->n_coll, 0, 4, st));
-        AGG_LAUNCH_ENR(k_agg_claim, dim3(fg), dim3(256), 0, st, C, P, a->tags, a->rows, rec_g, claims, a->n_claims,
-                           a->late, list_b, a->n_coll, a->err);
-        if (!P.packed) {
-            // hashed keys: the records that took a slot another record of this pass claimed are
-            // compared now that every key is written; the records of collided keys re-probe
-            // comparing keys
-            unsigned int nt = 0;
-            AGG_HIP(a, hipMemcpyAsync(&nt, a->n_coll, 4, hipMemcpyDeviceToHost, st));
+
+    // General path, first half: every record's group slot (rec_g)
+    int claim() {
+        hipLaunchKernelGGL(k_agg_recinfo, dim3(grid_for(NS, 256, 4096)), dim3(256), 0, st, out->sets, NS, out->dgrams, dginfo, a->plans, D,
+                           S, sctx, a->err);
+        if (n_blk) hipLaunchKernelGGL(k_agg_bset, dim3(grid_for(n_blk, 256, 4096)), dim3(256), 0, st, rstart, NS, n_blk, bset);
+        AGG_HIP(a, hipGetLastError());
+        if (P.has_bytes && n_rec) {
+            // byte values longer than 32 bytes: room in the arena for every tail this push can write.
+            // Key claims and ordered folds write at most one tail per group and field, and a push
+            // touches at most every slot of the table: the bound is the smaller of the records' tails
+            // and slots x byte fields x the longest tail (10^8 records of a 64-byte key over a few
+            // groups reserve 2 slots per group's worth, not 3 GB)
+            unsigned long long nd[2] = {0, 0};
+            AGG_HIP(a, hipMemsetAsync(a->arena_used + 1, 0, 16, st));
+            AGG_LAUNCH_ENR(k_agg_tail_need, dim3(grid_for(n_rec, 256, 4096)), dim3(256), 0, st, C, P, a->arena_used + 1);
+            AGG_HIP(a, hipMemcpyAsync(nd, a->arena_used + 1, 16, hipMemcpyDeviceToHost, st));
             AGG_HIP(a, hipStreamSynchronize(st));
+            uint32_t n_bval = 0;
+            for (uint32_t k = 0; k < P.n_keys; ++k) n_bval += P.key_kind[k] == KK_BYTES;
+            for (uint32_t v = 0; v < P.n_vals; ++v) n_bval += P.val_vc[v] == VC_VBYTES || P.val_vc[v] == VC_VLIST;
+            const uint64_t need = std::min<uint64_t>(nd[0], a->slots * n_bval * nd[1]);
+            if (int r = arena_reserve(a, need)) return undo.refuse(r, a->last_error);
+            P.arena = a->P.arena;
+            P.arena_cap = a->P.arena_cap;
+        }
+        undo.stage = PushUndo::claims;
+        if (n_rec) {
             AGG_HIP(a, hipMemsetAsync(a->n_coll, 0, 4, st));
-            if (nt)
-                AGG_LAUNCH_ENR(k_agg_check, dim3(grid_for(nt, 256, 1u << 20)), dim3(256), 0, st, C, P, a->rows, rec_g,
-                                   list_b, nt, list_a, a->n_coll, a->err);
-            for (int round = 0;; ++round) {
-                unsigned int nc = 0;
-                AGG_HIP(a, hipMemcpyAsync(&nc, a->n_coll, 4, hipMemcpyDeviceToHost, st));
+            AGG_LAUNCH_ENR(k_agg_claim, dim3(fg), dim3(256), 0, st, C, P, a->tags, a->rows, rec_g, claims, a->n_claims,
+                               a->late, list_b, a->n_coll, a->err);
+            if (!P.packed) {
+                // hashed keys: the records that took a slot another record of this pass claimed are
+                // compared now that every key is written; the records of collided keys re-probe
+                // comparing keys
+                unsigned int nt = 0;
+                AGG_HIP(a, hipMemcpyAsync(&nt, a->n_coll, 4, hipMemcpyDeviceToHost, st));
                 AGG_HIP(a, hipStreamSynchronize(st));
-                if (!nc) break;
-                if (round == 64) {
-                    AGG_HIP(a, hipMemcpyAsync(&n_claims, a->n_claims, 8, hipMemcpyDeviceToHost, st));
-                    AGG_HIP(a, hipStreamSynchronize(st));
-                    return rollback(NGZ_E_DEVICE, "key collision resolution did not converge");
-                }
-                // the records that met a slot being claimed join the next round's list with the collided ones
                 AGG_HIP(a, hipMemsetAsync(a->n_coll, 0, 4, st));
-                AGG_LAUNCH_ENR(k_agg_reprobe, dim3(grid_for(nc)), dim3(256), 0, st, C, P, a->tags, a->rows, rec_g,
-                                   list_a, nc, claims, a->n_claims, list_b, a->n_coll, a->err);
-                AGG_LAUNCH_ENR(k_agg_check, dim3(grid_for(nc)), dim3(256), 0, st, C, P, a->rows, rec_g, list_a, nc,
-                                   list_b, a->n_coll, a->err);
-                std::swap(list_a, list_b);
+                if (nt)
+                    AGG_LAUNCH_ENR(k_agg_check, dim3(grid_for(nt, 256, 1u << 20)), dim3(256), 0, st, C, P, a->rows, rec_g,
+                                       list_b, nt, list_a, a->n_coll, a->err);
+                for (int round = 0;; ++round) {
+                    unsigned int nc = 0;
+                    AGG_HIP(a, hipMemcpyAsync(&nc, a->n_coll, 4, hipMemcpyDeviceToHost, st));
+                    AGG_HIP(a, hipStreamSynchronize(st));
+                    if (!nc) break;
+                    if (round == 64) {
+                        AGG_HIP(a, hipMemcpyAsync(&n_claims, a->n_claims, 8, hipMemcpyDeviceToHost, st));
+                        AGG_HIP(a, hipStreamSynchronize(st));
+                        return undo.refuse(NGZ_E_DEVICE, "key collision resolution did not converge");
+                    }
+                    // the records that met a slot being claimed join the next round's list with the collided ones
+                    AGG_HIP(a, hipMemsetAsync(a->n_coll, 0, 4, st));
+                    AGG_LAUNCH_ENR(k_agg_reprobe, dim3(grid_for(nc)), dim3(256), 0, st, C, P, a->tags, a->rows, rec_g,
+                                       list_a, nc, claims, a->n_claims, list_b, a->n_coll, a->err);
+                    AGG_LAUNCH_ENR(k_agg_check, dim3(grid_for(nc)), dim3(256), 0, st, C, P, a->rows, rec_g, list_a, nc,
+                                       list_b, a->n_coll, a->err);
+                    std::swap(list_a, list_b);
+                }
             }
         }
+        AGG_HIP(a, hipGetLastError());
+        AGG_HIP(a, hipMemcpyAsync(&n_claims, a->n_claims, 8, hipMemcpyDeviceToHost, st));
+        AGG_HIP(a, hipMemcpyAsync(&errv, a->err, 4, hipMemcpyDeviceToHost, st));
+        AGG_HIP(a, hipStreamSynchronize(st));
+        if (errv & 16) { a->poisoned = true; return undo.refuse(NGZ_E_DEVICE, "set table entry out of range"); }
+        if (errv & 2) return undo.refuse(NGZ_AGG_E_OVERFLOW, "group table full");
+        if (a->live + n_claims > a->limit) return undo.refuse(NGZ_AGG_E_OVERFLOW, "more groups than the aggregator's capacity");
+        return NGZ_OK;
     }
-    AGG_HIP(a, hipGetLastError());
-    AGG_HIP(a, hipMemcpyAsync(&n_claims, a->n_claims, 8, hipMemcpyDeviceToHost, st));
-    AGG_HIP(a, hipMemcpyAsync(&errv, a->err, 4, hipMemcpyDeviceToHost, st));
-    AGG_HIP(a, hipStreamSynchronize(st));
-    if (errv & 16) { a->poisoned = true; return rollback(NGZ_E_DEVICE, "set table entry out of range"); }
-    if (errv & 2) return rollback(NGZ_AGG_E_OVERFLOW, "group table full");
-    if (a->live + n_claims > a->limit) return rollback(NGZ_AGG_E_OVERFLOW, "more groups than the aggregator's capacity");
-    // commit: every record has its group; reduce.  Few groups: a bounded grid whose workgroups
-    // walk many tiles, so the LDS combine table collects each group's records across them; many
-    // groups (about one record per group and push): one tile per workgroup, all records in flight
-    if (n_rec) {
+
+    // General path, second half: every record has its group; reduce.  Few groups: a bounded grid whose
+    // workgroups walk many tiles, so the LDS combine table collects each group's records across them;
+    // many groups (about one record per group and push): one tile per workgroup, all records in flight
+    int reduce() {
+        if (!n_rec) { AGG_HIP(a, hipGetLastError()); return NGZ_OK; }
         const uint32_t ag = (a->live + n_claims) * 8 > n_rec ? fg : ig;
+        // k_agg_apply over `grid` workgroups; with a list, only the records k_agg_apply_own listed
+        auto apply = [&](uint32_t grid, uint32_t *list, unsigned int *n_list) {
+            if (P.n_vals <= 8)
+                AGG_LAUNCH_ENR2(k_agg_apply, 8, dim3(grid), dim3(256), 0, st, C, P, rec_g, a->rows, list, n_list, a->err);
+            else
+                AGG_LAUNCH_ENR2(k_agg_apply, NGZ_AGG_MAX_VALUES, dim3(grid), dim3(256), 0, st, C, P, rec_g, a->rows, list,
+                                   n_list, a->err);
+        };
         // fused owner test (k_agg_apply_own first) only when the table holds many groups per
         // record after the claims: then nearly every record is its group's owner.  Few, hot
         // groups (a first push of a low-cardinality key included) would list almost every record
@@ -4027,16 +4010,9 @@ static int push_impl(ngz_agg *a, ngz_enrich *e, const std::vector<ngze::SlotResu
             const uint64_t nc = (uint64_t)np * nt + 1;
             size_t stb = 0;
             hipcub::DeviceScan::ExclusiveSum(nullptr, stb, (uint32_t *)nullptr, (uint32_t *)nullptr, (int)nc, st);
-            const size_t need = 2 * al(4 * nc) + al(stb) + (size_t)n_rec * pb;
-            if (need > a->part_cap) {
-                hipFree(a->part_buf);
-                a->part_buf = nullptr;
-                a->part_cap = 0;
-                if (hipMalloc(&a->part_buf, need) != hipSuccess) {
-                    a->poisoned = true;  // the claims are committed: this push cannot be undone here
-                    return fail(a, NGZ_E_NOMEM, "partition buffers");
-                }
-                a->part_cap = need;
+            if (!grow(a->part_buf, a->part_cap, 2 * al(4 * nc) + al(stb) + (size_t)n_rec * pb)) {
+                a->poisoned = true;  // the claims are committed: this push cannot be undone here
+                return fail(a, NGZ_E_NOMEM, "partition buffers");
             }
             uint32_t *counts = (uint32_t *)a->part_buf, *offs = (uint32_t *)(a->part_buf + al(4 * nc));
             void *stmp = a->part_buf + 2 * al(4 * nc);
@@ -4064,23 +4040,14 @@ static int push_impl(ngz_agg *a, ngz_enrich *e, const std::vector<ngze::SlotResu
             default: hipLaunchKernelGGL((k_agg_part_reduce<6, 4>), dim3(np), dim3(red_thr), 0, st, P, a->plans, offs, nt, pay, a->rows); break;
             }
         } else if (P.own && !split && groups * 8 > (uint64_t)n_rec) {
-
             // owners reduce their rows first, the records k_agg_apply_own lists apply atomics after
             AGG_HIP(a, hipMemsetAsync(a->n_coll, 0, 4, st));
             AGG_LAUNCH_ENR2(k_agg_apply_own, true, dim3(fg), dim3(256), 0, st, C, P, rec_g, a->rows, list_a, a->n_coll,
                                a->err);
-            if (P.n_vals <= 8)
-                AGG_LAUNCH_ENR2(k_agg_apply, 8, dim3(ig), dim3(256), 0, st, C, P, rec_g, a->rows, list_a, a->n_coll, a->err);
-            else
-                AGG_LAUNCH_ENR2(k_agg_apply, NGZ_AGG_MAX_VALUES, dim3(ig), dim3(256), 0, st, C, P, rec_g, a->rows, list_a,
-                                   a->n_coll, a->err);
+            apply(ig, list_a, a->n_coll);
         } else {
             // owner records (marked in rec_g) reduced after every other record
-            if (P.n_vals <= 8)
-                AGG_LAUNCH_ENR2(k_agg_apply, 8, dim3(ag), dim3(256), 0, st, C, P, rec_g, a->rows, nullptr, nullptr, a->err);
-            else
-                AGG_LAUNCH_ENR2(k_agg_apply, NGZ_AGG_MAX_VALUES, dim3(ag), dim3(256), 0, st, C, P, rec_g, a->rows, nullptr,
-                                   nullptr, a->err);
+            apply(ag, nullptr, nullptr);
             if (P.own)
                 AGG_LAUNCH_ENR2(k_agg_apply_own, false, dim3(fg), dim3(256), 0, st, C, P, rec_g, a->rows, nullptr, nullptr,
                                    a->err);
@@ -4091,43 +4058,95 @@ static int push_impl(ngz_agg *a, ngz_enrich *e, const std::vector<ngze::SlotResu
             void *stmp = a->rec_buf + B0 + 8 * R4;
             AGG_HIP(a, hipMemcpyAsync(sk, rec_g, 4ull * n_rec, hipMemcpyDeviceToDevice, st));
             hipLaunchKernelGGL(k_agg_iota, dim3(grid_for(n_rec)), dim3(256), 0, st, sv, (uint64_t)n_rec);
-            int end_bit = 1;
-            while (end_bit < 32 && (1ull << end_bit) <= a->slots) ++end_bit;
-            end_bit = 32;  // NONE (all ones) must sort after every slot
-            size_t tb = sort_tmp;
-            AGG_HIP(a, hipcub::DeviceRadixSort::SortPairs(stmp, tb, sk, sk2, sv, sv2, (int)n_rec, 0, end_bit, st));
+            size_t tb = sort_tmp;  // every key bit: NONE (all ones) must sort after every slot
+            AGG_HIP(a, hipcub::DeviceRadixSort::SortPairs(stmp, tb, sk, sk2, sv, sv2, (int)n_rec, 0, 32, st));
             AGG_LAUNCH_ENR(k_agg_ordered, dim3(grid_for(n_rec)), dim3(256), 0, st, C, P, sk2, sv2, (uint64_t)n_rec,
                                a->rows, a->err);
         }
+        AGG_HIP(a, hipGetLastError());
+        return NGZ_OK;
     }
-    AGG_HIP(a, hipGetLastError());
-    }
-done:
-    AGG_HIP(a, hipEventRecord(a->ev1, st));
-    uint32_t last_pm = 0;
-    unsigned long long late = 0, arena_now = a->arena_mark;
-    AGG_HIP(a, hipMemcpyAsync(&last_pm, pm + (D - 1), 4, hipMemcpyDeviceToHost, st));
-    AGG_HIP(a, hipMemcpyAsync(&late, a->late, 8, hipMemcpyDeviceToHost, st));
-    if (P.has_bytes) {
-        AGG_HIP(a, hipMemcpyAsync(&arena_now, a->arena_used, 8, hipMemcpyDeviceToHost, st));
-        AGG_HIP(a, hipMemcpyAsync(&errv, a->err, 4, hipMemcpyDeviceToHost, st));
-    }
-    AGG_HIP(a, hipStreamSynchronize(st));
-    if (P.has_bytes) {
-        a->arena_mark = arena_now;
-        if (errv & 64) {  // cannot happen: the push reserved every tail it writes
-            a->poisoned = true;
-            return fail(a, NGZ_E_DEVICE, "byte arena overrun");
+
+    int commit(uint64_t *late_records) {
+        AGG_HIP(a, hipEventRecord(a->ev1, st));
+        uint32_t last_pm = 0;
+        unsigned long long late = 0, arena_now = a->arena_mark;
+        AGG_HIP(a, hipMemcpyAsync(&last_pm, pm + (D - 1), 4, hipMemcpyDeviceToHost, st));
+        AGG_HIP(a, hipMemcpyAsync(&late, a->late, 8, hipMemcpyDeviceToHost, st));
+        if (P.has_bytes) {
+            AGG_HIP(a, hipMemcpyAsync(&arena_now, a->arena_used, 8, hipMemcpyDeviceToHost, st));
+            AGG_HIP(a, hipMemcpyAsync(&errv, a->err, 4, hipMemcpyDeviceToHost, st));
         }
+        AGG_HIP(a, hipStreamSynchronize(st));
+        if (P.has_bytes) {
+            a->arena_mark = arena_now;
+            if (errv & 64) {  // cannot happen: the push reserved every tail it writes
+                a->poisoned = true;
+                return fail(a, NGZ_E_DEVICE, "byte arena overrun");
+            }
+        }
+        hipEventElapsedTime(&a->t_push, a->ev0, a->ev1);
+        if (enr_rows) hipEventElapsedTime(&a->t_resolve, a->ev_r0, a->ev_r1);
+        a->live += n_claims;
+        if (last_pm > a->peer_time[pi]) a->peer_time[pi] = last_pm;
+        if (late_records) *late_records = late;
+        return NGZ_OK;
     }
-    hipEventElapsedTime(&a->t_push, a->ev0, a->ev1);
-    a->t_resolve = 0;
-    if (enr_rows) hipEventElapsedTime(&a->t_resolve, a->ev_r0, a->ev_r1);
-    a->live += n_claims;
-    if (last_pm > a->peer_time[pi]) a->peer_time[pi] = last_pm;
-    if (late_records) *late_records = late;
-    return NGZ_OK;
+};
+
+int PushUndo::refuse(int rc, const std::string &why) {
+    ngz_agg *a = ps->a;
+    const std::string msg = why;  // `why` may be a->last_error, which a failing upload_domains rewrites
+    if (stage == claims) {
+        if (ps->n_claims)
+            hipLaunchKernelGGL(k_agg_unclaim, dim3(grid_for(ps->n_claims)), dim3(256), 0, ps->st, a->tags, ps->claims,
+                               (uint64_t)ps->n_claims);
+        if (ps->P.has_bytes)  // the released claims' key tails: the arena as after the last push
+            hipMemcpyAsync(a->arena_used, &a->arena_mark, 8, hipMemcpyHostToDevice, ps->st);
+    }
+    if (new_peer) {
+        a->peers.pop_back();
+        a->peer_time.pop_back();
+        a->peer_index.erase(pk);
+    }
+    if (stage >= host) static_cast<AggDicts &>(*a) = kept;
+    if (stage >= domains) upload_domains(a);
+    if (stage == claims && hipStreamSynchronize(ps->st) != hipSuccess) a->poisoned = true;
+    return fail(a, rc, msg);
 }
+
+// ngz_agg_push, and with `enr` (an enricher's results for this batch) ngz_agg_push_enriched
+int push_impl(ngz_agg *a, ngz_enrich *e, const std::vector<ngze::SlotResult> *enr, ngz_ctx *ctx,
+              const ngz_batch_out *out, const ngz_peer *peer, int64_t collection_time_ms, uint64_t *late_records,
+              void *hip_stream) {
+    if (!a || !ctx || !out || !peer || (peer->family != 4 && peer->family != 6)) return NGZ_E_INVALID;
+    if (late_records) *late_records = 0;
+    a->last_path = "none";  // no record to reduce (set below otherwise)
+    a->t_resolve = 0;
+    if (a->poisoned) return fail(a, NGZ_AGG_E_POISONED, "aggregator failed earlier: ngz_agg_reset it");
+    AGG_HIP(a, hipSetDevice(a->device));
+    if (hip_stream) AGG_HIP(a, hipStreamSynchronize((hipStream_t)hip_stream));
+    PushState ps{a, out, enr, a->stream, out->n_slots, out->n_dgrams, out->n_sets};
+    ps.undo.ps = &ps;
+    if (int r = ps.enter(*peer)) return r;
+    if (int r = ps.build_slot_plans(ctx, e)) return r;
+    // Nothing to aggregate.  The peer's entry and its port's and templates' dictionary entries stay, on
+    // purpose: the push succeeded, and entries no group uses go at the next dict_gc or flush
+    if (!ps.D || !ps.NS) return NGZ_OK;
+    if (int r = ps.prologue(collection_time_ms)) return r;
+    bool done = false;
+    if (int r = ps.lowcard(done)) return r;
+    if (!done) {
+        a->last_path = "general";
+        if (int r = ps.claim()) return r;
+        if (int r = ps.reduce()) return r;
+    }
+    return ps.commit(late_records);
+}
+
+}  // namespace
+
+extern "C" {
 
 int ngz_agg_push(ngz_agg *a, ngz_ctx *ctx, const ngz_batch_out *out, const ngz_peer *peer,
                  int64_t collection_time_ms, uint64_t *late_records, void *hip_stream) {
@@ -4160,16 +4179,7 @@ int64_t ngz_agg_flush(ngz_agg *a, void *dst, uint64_t cap) {
     if (n < 0) return n;
     // WindowAggregator::flush: every window out, the event times forgotten; the set and
     // peer dictionaries start over (the rows just returned refer to out_*)
-    forget_peers(a);
-    a->templates.clear();
-    a->ports.clear();
-    a->domains.clear();
-    a->live = a->tombs = 0;
-    int rc = reset_rows(a, a->tags, a->rows);
-    if (rc == NGZ_OK) rc = upload_domains(a);
-    if (rc == NGZ_OK) rc = arena_clear(a);
-    if (rc != NGZ_OK) return rc;
-    AGG_HIP(a, hipStreamSynchronize(a->stream));
+    if (int rc = clear_all(a)) return rc;
     return n;
 }
 
@@ -4216,17 +4226,7 @@ int ngz_agg_reset(ngz_agg *a) {
     if (!a) return NGZ_E_INVALID;
     AGG_HIP(a, hipSetDevice(a->device));
     a->poisoned = false;
-    forget_peers(a);
-    a->templates.clear();
-    a->ports.clear();
-    a->domains.clear();
-    a->live = a->tombs = 0;
-    int rc = reset_rows(a, a->tags, a->rows);
-    if (rc == NGZ_OK) rc = upload_domains(a);
-    if (rc == NGZ_OK) rc = arena_clear(a);
-    if (rc != NGZ_OK) return rc;
-    AGG_HIP(a, hipStreamSynchronize(a->stream));
-    return NGZ_OK;
+    return clear_all(a);
 }
 
 int ngz_agg_sets(ngz_agg *a, uint32_t *templates, uint32_t *n_templates, uint16_t *ports, uint32_t *n_ports,

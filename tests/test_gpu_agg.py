@@ -395,24 +395,136 @@ def test_closed_windows_free_dictionary_entries(dev):
     same_groups(agg.flush(), o.flush())
 
 
-def test_failed_push_leaves_the_aggregator_unchanged(dev):
+def long_key_datagrams(names, export_time, template=False):
+    """interfaceName sent variable-length, one record per name (names longer than 32 bytes keep
+    their tails in the byte arena)."""
+    recs = [_vlen(n.encode()) + struct.pack(">Q", i + 1) for i, n in enumerate(names)]
+    return [ipfix_msg(([tset(256, [(82, 0xFFFF), (1, 8)])] if template else []) + [dset(256, recs)], export_time)]
+
+
+@pytest.mark.parametrize("case", ["general", "long_byte_keys", "lowcard_by_size", "lowcard_forced"])
+def test_failed_push_leaves_the_aggregator_unchanged(dev, case, monkeypatch):
     """A push that would exceed the capacity fails without touching the groups, the set
-    dictionaries or the event time: the flush afterwards equals the oracle of the pushes
-    that succeeded."""
-    from netgauze_amd.aggregate import AggError, FlowAggregator
+    dictionaries or the event time, and a valid push after it is taken: the flush afterwards
+    equals the oracle of the pushes that succeeded.  With a byte key of more than 32 bytes the
+    refused push's key tails are given back to the arena (the third push's new tails land where
+    they would have without it); with a packed key and NGZ_AGG_OPT_LOWCARD 1 the refusal comes
+    out of k_agg_lc_merge."""
+    from netgauze_amd.aggregate import AggError
     from netgauze_amd.flow import FlowInfoCodec
-    fields = [(0, 11, 0, OK)] + T20_AGG
-    a = t20_datagrams(400, 100, [1_700_000_000])
-    b = t20_datagrams(4000, 100, [1_700_000_030], seed_first=777)[1:]
-    codec = FlowInfoCodec()
-    o = A.aggregate_datagrams(fields, a, peer_port=1, collection_ms=5)
+    import ngz_oracle as O
+    if case == "long_byte_keys":
+        fields = [(0, 82, 0, OK), (0, 1, 0, ADD)]
+        name = "interface-%04d-with-a-name-longer-than-thirty-two-bytes-%s"
+        a = long_key_datagrams([name % (j, "a") for j in range(60)], 1_700_000_000, template=True)
+        b = long_key_datagrams([name % (j, "b") for j in range(300)], 1_700_000_010)
+        # in a's window: eight new keys, eight of a's
+        c = long_key_datagrams([name % (j, "c" if j % 2 else "a") for j in range(16)], 1_700_000_020)
+        room = 10
+    else:
+        lowcard = case.startswith("lowcard")
+        # lowcard: protocol + direction, a packed key of 6 tuples per window
+        fields = ([(0, 4, 0, OK), (0, 61, 0, OK)] if lowcard else [(0, 11, 0, OK)]) + T20_AGG
+        if lowcard:
+            monkeypatch.setitem(AGG_OPTIONS, _opt("NGZ_AGG_OPT_LOWCARD"), 1 if case == "lowcard_forced" else -1)
+        a = t20_datagrams(400, 100, [1_700_000_000])
+        # lowcard: six more windows of 6 groups; general: thousands of destination ports
+        b = t20_datagrams(600 if lowcard else 4000, 100, [1_700_000_030 + (600 if lowcard else 0)], seed_first=777)[1:]
+        c = a[-1:]  # the newest message again: its groups' values move on
+        room = 3 if lowcard else 10
+    codec, oc = FlowInfoCodec(), O.FlowInfoCodec()
+    o = A.aggregate_datagrams(fields, a, peer_port=1, collection_ms=5, codec=oc)
     n_a = len(o.groups) + len(o.closed)
-    agg = new_agg(fields, capacity=n_a + 10)
+    agg = new_agg(fields, capacity=n_a + room)
     agg.push(codec.decode_datagrams(a), 1, 5)
+    if case == "lowcard_forced":
+        assert agg.last_path() == "lowcard"
     with pytest.raises(AggError, match="capacity|table full"):
         agg.push(codec.decode_datagrams(b), 2, 9)
     assert agg.n_groups() == n_a
+    # the refusal came out of the path meant: the general path names itself before it claims
+    assert agg.last_path() == ("none" if case == "lowcard_forced" else "general")
+    agg.push(codec.decode_datagrams(c), 1, 7)
+    if case == "lowcard_forced":
+        assert agg.last_path() == "lowcard"
+    A.aggregate_datagrams(fields, c, 1, 7, agg=o, codec=oc)
+    assert agg.n_groups() == len(o.groups) + len(o.closed)
+    got = agg.emit() + agg.flush()
+    same_groups(got, o.emit() + o.flush())
+    assert all(g["ports"] == {1} for g in got)
+    if case == "long_byte_keys":
+        assert sum(len(g["key"][0]) > 32 for g in got) == 60 + 8
+
+
+def test_peer_limit_refusal_keeps_the_aggregator(dev):
+    """A push from a third peer IP with max_peers 2 is refused before anything else is touched:
+    the groups stay, the two peers keep their entries and a push from one of them is taken; the
+    flush equals the oracle of the pushes that succeeded and names two peers."""
+    from netgauze_amd.aggregate import AggError
+    from netgauze_amd.flow import FlowInfoCodec
+    import ngz_oracle as O
+    fields = [(0, 4, 0, OK)] + T20_AGG
+    d = t20_datagrams(300, 100, [1_700_000_000])
+    ips = ["10.0.0.1", "2001:db8::2", "10.0.0.3"]
+    agg = new_agg(fields, max_peers=2)
+    o = A.FlowAggregatorOracle(fields, 60, 10)
+    codecs, ocodecs = [FlowInfoCodec() for _ in ips], [O.FlowInfoCodec() for _ in ips]
+    for i in (0, 1):
+        agg.push(codecs[i].decode_datagrams(d[:3]), 4739, 5, peer_ip=ips[i])
+        A.aggregate_datagrams(fields, d[:3], 4739, 5, peer_ip=ips[i], agg=o, codec=ocodecs[i])
+    n = agg.n_groups()
+    assert n == len(o.groups) + len(o.closed) and n > 0
+    with pytest.raises(AggError, match="max_peers"):
+        agg.push(codecs[2].decode_datagrams(d), 4739, 5, peer_ip=ips[2])
+    assert agg.n_groups() == n
+    agg.push(codecs[0].decode_datagrams(d[3:]), 4739, 6, peer_ip=ips[0])
+    A.aggregate_datagrams(fields, d[3:], 4739, 6, peer_ip=ips[0], agg=o, codec=ocodecs[0])
     same_groups(agg.emit() + agg.flush(), o.emit() + o.flush())
+    assert len(agg.peers()) == 2
+
+
+def test_plan_refusal_after_dictionary_insertions(dev):
+    """A batch whose template the aggregator cannot take is refused after the push gave its new
+    peer port and template id dictionary entries and fixed the first key's width at first sight:
+    all of it is taken back.  Decode fixes a column's width by the IE's type, so no IE arrives at
+    two widths; the refusal used is "fixed-size key field sent variable-length": template 257
+    declares mplsTopLabelStackSection (a [u8; 3] octetArray, which the template parser takes at
+    any length) 4 bytes long, so its records fail to decode.  layout() is as before, a further
+    push (a third template, a third port) is taken, the flush equals the oracle of the pushes
+    that succeeded, and its sets hold neither template 257 nor port 5000."""
+    from netgauze_amd.aggregate import AggError
+    from netgauze_amd.flow import FlowInfoCodec
+    import kat_runner as KR
+    import kats_packets as KP
+    import ngz_oracle as O
+    fields = [(0, 7, 0, OK), (0, 4, 0, OK), (0, 70, 0, OK), (0, 1, 0, ADD)]
+    port_s, proto, octets = (KP.S("sourceTransportPort", 2), KP.S("protocolIdentifier", 1),
+                             KP.S("octetDeltaCount", 8))
+    tpl = lambda tid, *specs: KR.template_datagram(10, tid, (), specs)  # noqa: E731  (observation domain 0)
+    data = lambda tid, recs, t: ipfix_msg([dset(tid, recs)], t, domain=0)  # noqa: E731
+    p1 = [tpl(256, proto, octets), data(256, [struct.pack(">BQ", 6 + j % 2, j + 1) for j in range(40)], 1_700_000_000)]
+    bad = [tpl(257, port_s, proto, KP.S("mplsTopLabelStackSection", 4), octets),
+           data(257, [struct.pack(">HB4sQ", 80 + j, 6, b"\0\1\2\3", j + 1) for j in range(40)], 1_700_000_010)]
+    p3 = [tpl(258, port_s, proto, octets),
+          data(258, [struct.pack(">HBQ", 80 + j % 5, 6 + j % 2, j + 1) for j in range(40)], 1_700_000_020),
+          data(256, [struct.pack(">BQ", 17, j + 1) for j in range(10)], 1_700_000_020)]
+    codec, oc = FlowInfoCodec(), O.FlowInfoCodec()
+    agg = new_agg(fields, max_peers=256)
+    agg.push(codec.decode_datagrams(p1), 4739, 5)
+    o = A.aggregate_datagrams(fields, p1, 4739, 5, codec=oc)
+    layout, n = agg.layout(), agg.n_groups()
+    assert layout[2] == [0, 1, 0]  # sourceTransportPort not seen yet
+    with pytest.raises(AggError, match="fixed-size key field sent variable-length"):
+        agg.push(codec.decode_datagrams(bad), 5000, 6)
+    assert agg.layout() == layout and agg.n_groups() == n
+    agg.push(codec.decode_datagrams(p3), 4740, 7)
+    A.aggregate_datagrams(fields, p3, 4740, 7, agg=o, codec=oc)
+    assert agg.layout()[2] == [2, 1, 0]
+    got = agg.flush()
+    same_groups(got, o.flush())
+    templates, ports, _domains = agg.sets()
+    assert {t & 0xFFFF for t in templates if t != 0xFFFFFFFF} == {256, 258}
+    assert {p for p in ports if p != 0xFFFF} == {4739, 4740}
 
 
 def test_ordered_reductions(dev):
