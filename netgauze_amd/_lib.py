@@ -96,6 +96,23 @@ NGZ_OPTIONS_OPTIONS = 0x100
 NGZ_OPTIONS_MAX_REFS = 24
 OPTIONS_CLASSES = {0: "none", 1: "sampling", 2: "interface", 3: "vrf", 4: "unclassified"}
 OPTIONS_OUTCOMES = {0: "ops", 1: "not_options", 2: "conversion_error", 3: "missing_required_fields"}
+# include/ngz/flow_output.h
+OUTPUT_FUNCTIONS = [
+    "ngz_output_abi_version", "ngz_output_create", "ngz_output_destroy", "ngz_output_last_error", "ngz_output_schema",
+    "ngz_output_template_plan", "ngz_output_encode", "ngz_output_slot", "ngz_output_to_host", "ngz_output_totals",
+    "ngz_output_last_timing", "ngz_output_last_launches", "ngz_output_set_option",
+]
+NGZ_OUTPUT_OPT_RECOMPUTE, NGZ_OUTPUT_OPT_IMAGE = 1, 2
+NGZ_OUTPUT_ABI_VERSION = 1
+NGZ_OUTPUT_OPTIONS = 0x100
+NGZ_OUTPUT_MAX_FIELDS, NGZ_OUTPUT_MAX_REFS, NGZ_OUTPUT_GUARD = 64, 10, 64
+NGZ_OUTPUT_E_UNSUPPORTED, NGZ_OUTPUT_E_CONFIG = -20, -21
+OUTPUT_SELECTS = {"Single": 0, "Coalesce": 1, "Multi": 2, "Layer2SegmentId": 3}
+OUTPUT_TRANSFORMS = {"Identity": 0, "String": 1, "MplsIndex": 2, "TrimmedString": 3, "LowercaseString": 4,
+                     "TimestampMillisString": 5, "Rename": 6, "StringArray": 7, "StringArrayAgg": 8, "StringMapAgg": 9}
+OUTPUT_DEFAULTS = {"Bytes": 1, "U8": 2, "U16": 3, "U32": 4, "U64": 5, "I8": 6, "I16": 7, "I32": 8, "I64": 9, "F32": 10,
+                   "F64": 11, "Boolean": 12, "String": 13, "TimestampMillis": 14, "StringArray": 15, "StringMap": 16}
+OUTPUT_TYPES = {1: "int", 2: "long", 3: "float", 4: "double", 5: "boolean", 6: "string", 7: "bytes", 8: "array"}
 NGZ_ENRICH_MAX_SCOPE_FIELDS, NGZ_ENRICH_MAX_SHAPES, NGZ_ENRICH_MAX_COLUMNS = 4, 8, 32
 NGZ_ENRICH_MAX_KEY_BYTES, NGZ_ENRICH_MAX_DOMAINS = 16, 253
 NGZ_RENORM_OPTIONS = 0x100
@@ -345,6 +362,36 @@ class OptionsPlan(ctypes.Structure):
 assert ctypes.sizeof(OptionsPlan) == 972 and ctypes.sizeof(OptionsStats) == 48
 
 
+class OutputField(ctypes.Structure):
+    """ngz_output_field: one FieldConfig."""
+    _fields_ = [("name", ctypes.c_char_p), ("select", ctypes.c_uint8), ("transform", ctypes.c_uint8),
+                ("default_kind", ctypes.c_uint8), ("encap_type", ctypes.c_uint8), ("encap_unassigned", ctypes.c_uint8),
+                ("reserved", ctypes.c_uint8 * 3), ("n_refs", ctypes.c_uint32), ("refs", ctypes.POINTER(EnrichRef)),
+                ("default_scalar", ctypes.c_uint64), ("default_bytes", ctypes.c_char_p), ("default_len", ctypes.c_uint32),
+                ("reserved2", ctypes.c_uint32)]
+
+
+class OutputFieldPlan(ctypes.Structure):
+    _fields_ = [("avro_type", ctypes.c_uint8), ("nullable", ctypes.c_uint8), ("n_present", ctypes.c_uint8),
+                ("reserved", ctypes.c_uint8), ("src", ctypes.c_int16 * 10)]
+
+
+class OutputPlan(ctypes.Structure):
+    """ngz_output_plan (ngz_output_template_plan)."""
+    _fields_ = [("n_fields", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("f", OutputFieldPlan * 64)]
+
+
+class OutputStats(ctypes.Structure):
+    """ngz_output_stats."""
+    _fields_ = [("rows", ctypes.c_uint64), ("rows_failed", ctypes.c_uint64), ("bytes", ctypes.c_uint64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+assert (ctypes.sizeof(OutputField), ctypes.sizeof(OutputFieldPlan), ctypes.sizeof(OutputPlan), ctypes.sizeof(OutputStats)) == (56, 24, 1544, 24)
+
+
 assert (ctypes.sizeof(EnrichPeer), ctypes.sizeof(EnrichField), ctypes.sizeof(EnrichIe), ctypes.sizeof(EnrichOperation),
         ctypes.sizeof(EnrichResolved), ctypes.sizeof(EnrichStats), ctypes.sizeof(EnrichColumn)) == (20, 24, 8, 64, 24, 32, 24)
 
@@ -591,6 +638,35 @@ def load():
     lib.ngz_options_last_timing.restype = I
     lib.ngz_options_last_launches.argtypes = [P]
     lib.ngz_options_last_launches.restype = I
+    # flow output (flow_output.h)
+    lib.ngz_output_abi_version.argtypes, lib.ngz_output_abi_version.restype = [], I
+    if lib.ngz_output_abi_version() != NGZ_OUTPUT_ABI_VERSION:
+        raise RuntimeError("netgauze_amd: %s has flow-output ABI version %d, this binding needs %d -- rebuild it"
+                           % (LIB_PATH, lib.ngz_output_abi_version(), NGZ_OUTPUT_ABI_VERSION))
+    lib.ngz_output_create.argtypes = [I, ctypes.POINTER(OutputField), U32, ctypes.POINTER(P), ctypes.c_char_p, ctypes.c_size_t]
+    lib.ngz_output_create.restype = I
+    lib.ngz_output_destroy.argtypes = [P]
+    lib.ngz_output_destroy.restype = None
+    lib.ngz_output_last_error.argtypes = [P]
+    lib.ngz_output_last_error.restype = ctypes.c_char_p
+    lib.ngz_output_schema.argtypes = [P, ctypes.c_char_p, ctypes.c_size_t]
+    lib.ngz_output_schema.restype = ctypes.c_int64
+    lib.ngz_output_template_plan.argtypes = [P, P, ctypes.c_size_t, I, ctypes.POINTER(OutputPlan)]
+    lib.ngz_output_template_plan.restype = I
+    lib.ngz_output_encode.argtypes = [P, P, ctypes.POINTER(BatchOut), ctypes.POINTER(OutputStats), P]
+    lib.ngz_output_encode.restype = I
+    lib.ngz_output_slot.argtypes = [P, U32, ctypes.POINTER(P), ctypes.POINTER(P), ctypes.POINTER(U64), ctypes.POINTER(U64)]
+    lib.ngz_output_slot.restype = I
+    lib.ngz_output_to_host.argtypes = [P, U32, P, U64, P, U64]
+    lib.ngz_output_to_host.restype = I
+    lib.ngz_output_totals.argtypes = [P, ctypes.POINTER(OutputStats), I]
+    lib.ngz_output_totals.restype = I
+    lib.ngz_output_last_timing.argtypes = [P, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
+    lib.ngz_output_last_timing.restype = I
+    lib.ngz_output_last_launches.argtypes = [P]
+    lib.ngz_output_last_launches.restype = I
+    lib.ngz_output_set_option.argtypes = [P, I, ctypes.c_int64]
+    lib.ngz_output_set_option.restype = I
     # ingest (flow_ingest.h)
     lib.ngz_pcap_open.argtypes = [ctypes.c_char_p, ctypes.POINTER(P)]
     lib.ngz_pcap_open.restype = I

@@ -1,4 +1,4 @@
-// What the post-decode stages share (ngz_renorm.hip, ngz_enrich.hip, ngz_options.hip; included by
+// What the post-decode stages share (ngz_renorm.hip, ngz_enrich.hip, ngz_options.hip, ngz_output.hip; included by
 // those units only): the device helpers of their set and row kernels, and the host scaffold of a
 // stage handle.  Header only.
 #pragma once
