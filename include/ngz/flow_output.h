@@ -52,8 +52,8 @@
  * Rows.  One datum per row of every slot, in the slot's stream order (pair rows with (datagram, set,
  * record) through the set table, as ngz_record_fields does).  Rows of a datagram whose status is not
  * NGZ_DG_OK give a zero-length datum and are counted (rows_failed).  A slot none of whose fields can be
- * present still gives its rows: nulls and defaults.  The plan reads a slot's own columns only (no
- * enrichment columns, no aggregated rows).
+ * present still gives its rows: nulls and defaults.  The plan reads a slot's own columns only: no
+ * enrichment columns; aggregated rows, what the Avro publisher sends, are flow_agg_output.h's.
  *
  * Output, per batch slot, in device memory the stage owns until its next encode: `bytes`, the datums
  * back to back in row order, and `offsets[n_rows + 1]` (u64): row r is bytes[offsets[r], offsets[r+1]).

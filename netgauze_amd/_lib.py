@@ -113,6 +113,13 @@ OUTPUT_TRANSFORMS = {"Identity": 0, "String": 1, "MplsIndex": 2, "TrimmedString"
 OUTPUT_DEFAULTS = {"Bytes": 1, "U8": 2, "U16": 3, "U32": 4, "U64": 5, "I8": 6, "I16": 7, "I32": 8, "I64": 9, "F32": 10,
                    "F64": 11, "Boolean": 12, "String": 13, "TimestampMillis": 14, "StringArray": 15, "StringMap": 16}
 OUTPUT_TYPES = {1: "int", 2: "long", 3: "float", 4: "double", 5: "boolean", 6: "string", 7: "bytes", 8: "array"}
+# include/ngz/flow_agg_output.h
+AGG_OUTPUT_FUNCTIONS = [
+    "ngz_agg_output_abi_version", "ngz_agg_output_create", "ngz_agg_output_destroy", "ngz_agg_output_last_error",
+    "ngz_agg_output_schema", "ngz_agg_output_encode", "ngz_agg_output_result", "ngz_agg_output_to_host",
+    "ngz_agg_output_last_timing", "ngz_agg_output_last_launches",
+]
+NGZ_AGG_OUTPUT_ABI_VERSION = 1
 NGZ_ENRICH_MAX_SCOPE_FIELDS, NGZ_ENRICH_MAX_SHAPES, NGZ_ENRICH_MAX_COLUMNS = 4, 8, 32
 NGZ_ENRICH_MAX_KEY_BYTES, NGZ_ENRICH_MAX_DOMAINS = 16, 253
 NGZ_RENORM_OPTIONS = 0x100
@@ -392,6 +399,14 @@ class OutputStats(ctypes.Structure):
 assert (ctypes.sizeof(OutputField), ctypes.sizeof(OutputFieldPlan), ctypes.sizeof(OutputPlan), ctypes.sizeof(OutputStats)) == (56, 24, 1544, 24)
 
 
+class AggOutputStats(ctypes.Structure):
+    """ngz_agg_output_stats."""
+    _fields_ = [("rows", ctypes.c_uint64), ("bytes", ctypes.c_uint64), ("tail_bytes", ctypes.c_uint64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 assert (ctypes.sizeof(EnrichPeer), ctypes.sizeof(EnrichField), ctypes.sizeof(EnrichIe), ctypes.sizeof(EnrichOperation),
         ctypes.sizeof(EnrichResolved), ctypes.sizeof(EnrichStats), ctypes.sizeof(EnrichColumn)) == (20, 24, 8, 64, 24, 32, 24)
 
@@ -667,6 +682,29 @@ def load():
     lib.ngz_output_last_launches.restype = I
     lib.ngz_output_set_option.argtypes = [P, I, ctypes.c_int64]
     lib.ngz_output_set_option.restype = I
+    # Avro datums of aggregated groups (flow_agg_output.h)
+    lib.ngz_agg_output_abi_version.argtypes, lib.ngz_agg_output_abi_version.restype = [], I
+    if lib.ngz_agg_output_abi_version() != NGZ_AGG_OUTPUT_ABI_VERSION:
+        raise RuntimeError("netgauze_amd: %s has aggregated-output ABI version %d, this binding needs %d -- rebuild it"
+                           % (LIB_PATH, lib.ngz_agg_output_abi_version(), NGZ_AGG_OUTPUT_ABI_VERSION))
+    lib.ngz_agg_output_create.argtypes = [I, ctypes.POINTER(OutputField), U32, ctypes.POINTER(P), ctypes.c_char_p, ctypes.c_size_t]
+    lib.ngz_agg_output_create.restype = I
+    lib.ngz_agg_output_destroy.argtypes = [P]
+    lib.ngz_agg_output_destroy.restype = None
+    lib.ngz_agg_output_last_error.argtypes = [P]
+    lib.ngz_agg_output_last_error.restype = ctypes.c_char_p
+    lib.ngz_agg_output_schema.argtypes = [P, ctypes.c_char_p, ctypes.c_size_t]
+    lib.ngz_agg_output_schema.restype = ctypes.c_int64
+    lib.ngz_agg_output_encode.argtypes = [P, P, P, U64, ctypes.POINTER(AggOutputStats), P]
+    lib.ngz_agg_output_encode.restype = I
+    lib.ngz_agg_output_result.argtypes = [P, ctypes.POINTER(P), ctypes.POINTER(P), ctypes.POINTER(U64), ctypes.POINTER(U64)]
+    lib.ngz_agg_output_result.restype = I
+    lib.ngz_agg_output_to_host.argtypes = [P, P, U64, P, U64]
+    lib.ngz_agg_output_to_host.restype = I
+    lib.ngz_agg_output_last_timing.argtypes = [P] + [ctypes.POINTER(ctypes.c_float)] * 3
+    lib.ngz_agg_output_last_timing.restype = I
+    lib.ngz_agg_output_last_launches.argtypes = [P]
+    lib.ngz_agg_output_last_launches.restype = I
     # ingest (flow_ingest.h)
     lib.ngz_pcap_open.argtypes = [ctypes.c_char_p, ctypes.POINTER(P)]
     lib.ngz_pcap_open.restype = I

@@ -7,8 +7,8 @@
 //   a hipcub exclusive scan: the u64 offsets,
 //   k_output_pack  a wave encodes its 64 consecutive rows into an LDS image laid out like the output
 //                  range they fill, and copies the image out in 16-byte stores.
-// One set of encoders (templated on a counting or a storing writer) serves both passes, so the sizes
-// are the packed bytes by construction.
+// One set of encoders (templated on a counting or a storing writer, ngz_output_enc.h, shared with
+// ngz_agg_output.hip) serves both passes, so the sizes are the packed bytes by construction.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
@@ -19,11 +19,13 @@
 
 #include "ngz/flow_output.h"
 #include "ngz_host.h"
+#include "ngz_output_enc.h"
 #include "ngz_output_plan.h"
 #include "ngz_stage.h"
 
 namespace {
 
+using namespace ngzenc;
 using ngzout::Enc;
 
 constexpr uint32_t OUT_THREADS = 256;
@@ -76,179 +78,6 @@ struct OutPlan {
     unsigned long long bytes_size;
     unsigned long long *counters;
 };
-
-// ---------------------------------------------------------------------------------------------
-// writers and encoders
-// ---------------------------------------------------------------------------------------------
-struct CountW {
-    static constexpr bool counting = true;
-    uint32_t n = 0;
-    __device__ __forceinline__ void put(uint32_t) { ++n; }
-    __device__ __forceinline__ void bytes(const uint8_t *, uint32_t len) { n += len; }
-};
-struct PutW {  // nothing is stored at or past `end`
-    static constexpr bool counting = false;
-    uint8_t *p, *end;
-    __device__ __forceinline__ void put(uint32_t b) {
-        if (p < end) *p = (uint8_t)b;
-        ++p;
-    }
-    __device__ __forceinline__ void bytes(const uint8_t *s, uint32_t len) {
-        for (uint32_t i = 0; i < len; ++i) put(s[i]);
-    }
-};
-
-template <class W>
-__device__ __forceinline__ void put_varint(W &w, uint64_t z) {
-    if constexpr (W::counting) {
-        w.n += (70u - (uint32_t)__clzll((long long)(z | 1))) / 7u;
-    } else {
-        while (z >= 0x80) {
-            w.put((uint32_t)z | 0x80u);
-            z >>= 7;
-        }
-        w.put((uint32_t)z);
-    }
-}
-template <class W>
-__device__ __forceinline__ void put_long(W &w, int64_t v) {
-    put_varint(w, ((uint64_t)v << 1) ^ (uint64_t)(v >> 63));
-}
-template <class W>
-__device__ __forceinline__ void put_dec(W &w, uint64_t v) {
-    uint8_t buf[20];
-    uint32_t n = 0;
-    do {
-        buf[n++] = (uint8_t)('0' + v % 10);
-        v /= 10;
-    } while (v);
-    if constexpr (W::counting) w.n += n;
-    else
-        while (n) w.put(buf[--n]);
-}
-template <class W>
-__device__ __forceinline__ void put_ip4(W &w, uint32_t v) {
-    for (int i = 3; i >= 0; --i) {
-        put_dec(w, (v >> (8 * i)) & 255u);
-        if (i) w.put('.');
-    }
-}
-template <class W>
-__device__ __forceinline__ void put_hex(W &w, uint32_t d) { w.put(d < 10 ? '0' + d : 'a' + d - 10); }
-template <class W>
-__device__ __forceinline__ void put_seg(W &w, uint32_t s) {  // {:x} of one 16-bit segment
-    if (s >> 12) put_hex(w, s >> 12);
-    if (s >> 8) put_hex(w, (s >> 8) & 15u);
-    if (s >> 4) put_hex(w, (s >> 4) & 15u);
-    put_hex(w, s & 15u);
-}
-// core::net::Ipv6Addr Display: ::ffff:a.b.c.d for a v4-mapped address, else the longest run of two
-// or more zero segments (the first of equals) as "::"
-template <class W>
-__device__ __forceinline__ void put_ip6(W &w, const uint8_t *b) {
-    uint32_t s[8];
-    for (int i = 0; i < 8; ++i) s[i] = ((uint32_t)b[2 * i] << 8) | b[2 * i + 1];
-    if (!(s[0] | s[1] | s[2] | s[3] | s[4]) && s[5] == 0xFFFFu) {
-        const char pre[7] = {':', ':', 'f', 'f', 'f', 'f', ':'};
-        for (int i = 0; i < 7; ++i) w.put(pre[i]);
-        put_ip4(w, (s[6] << 16) | s[7]);
-        return;
-    }
-    int best_s = 0, best_l = 0, cur_s = 0, cur_l = 0;
-    for (int i = 0; i < 8; ++i) {
-        if (s[i]) {
-            cur_l = 0;
-            continue;
-        }
-        if (!cur_l) cur_s = i;
-        if (++cur_l > best_l) {
-            best_s = cur_s;
-            best_l = cur_l;
-        }
-    }
-    if (best_l < 2) best_l = 0;
-    for (int i = 0; i < 8; ++i) {
-        if (best_l && i == best_s) {
-            w.put(':');
-            w.put(':');
-            i += best_l - 1;
-            continue;
-        }
-        if (i && !(best_l && i == best_s + best_l)) w.put(':');
-        put_seg(w, s[i]);
-    }
-}
-// An Avro string whose text `body` writes: its length, then the text
-template <class W, class F>
-__device__ __forceinline__ void put_text(W &w, F &&body) {
-    CountW c;
-    body(c);
-    put_varint(w, (uint64_t)c.n << 1);
-    if constexpr (W::counting) w.n += c.n;
-    else body(w);
-}
-
-struct Cell {
-    uint64_t v;        // an integer, float or IPv4 column's cell, zero-extended
-    const uint8_t *p;  // any other cell's bytes
-    uint32_t n;
-};
-
-__device__ __forceinline__ bool enc_numeric(uint32_t enc) {
-    return enc == ngzout::ENC_INT_U || enc == ngzout::ENC_INT_S || enc == ngzout::ENC_RAW || enc == ngzout::ENC_BOOL ||
-           enc == ngzout::ENC_IP4 || enc == ngzout::ENC_DEC_U || enc == ngzout::ENC_DEC_S || enc == ngzout::ENC_BOOLSTR;
-}
-
-template <class W>
-__device__ __forceinline__ void encode_value(W &w, const OutSource &S, const Cell &c) {
-    const int shift = 64 - 8 * (int)S.width;
-    switch (S.enc) {
-    case ngzout::ENC_INT_U: put_long(w, (int64_t)c.v); break;
-    case ngzout::ENC_INT_S: put_long(w, (int64_t)(c.v << shift) >> shift); break;
-    case ngzout::ENC_RAW:
-        for (uint32_t b = 0; b < S.width; ++b) w.put((uint32_t)(c.v >> (8 * b)) & 255u);
-        break;
-    case ngzout::ENC_BOOL: w.put(c.v ? 1 : 0); break;
-    case ngzout::ENC_STR:
-    case ngzout::ENC_BYTES:
-        put_varint(w, (uint64_t)c.n << 1);
-        w.bytes(c.p, c.n);
-        break;
-    case ngzout::ENC_MAC:
-        put_text(w, [&](auto &t) {
-            for (int i = 0; i < 6; ++i) {
-                if (i) t.put(':');
-                put_hex(t, c.p[i] >> 4);
-                put_hex(t, c.p[i] & 15u);
-            }
-        });
-        break;
-    case ngzout::ENC_IP4: put_text(w, [&](auto &t) { put_ip4(t, (uint32_t)c.v); }); break;
-    case ngzout::ENC_IP6: put_text(w, [&](auto &t) { put_ip6(t, c.p); }); break;
-    case ngzout::ENC_DEC_U: put_text(w, [&](auto &t) { put_dec(t, c.v); }); break;
-    case ngzout::ENC_DEC_S: {
-        const int64_t sv = (int64_t)(c.v << shift) >> shift;
-        put_text(w, [&](auto &t) {
-            if (sv < 0) t.put('-');
-            put_dec(t, sv < 0 ? 0ull - (uint64_t)sv : (uint64_t)sv);
-        });
-        break;
-    }
-    case ngzout::ENC_BOOLSTR:
-        put_text(w, [&](auto &t) {
-            const char *s = c.v ? "true" : "false";
-            for (uint32_t i = 0; i < (c.v ? 4u : 5u); ++i) t.put(s[i]);
-        });
-        break;
-    case ngzout::ENC_MPLS_ITEM:
-        put_text(w, [&](auto &t) {
-            put_dec(t, S.aux);
-            t.put('-');
-            put_dec(t, ((uint32_t)c.p[0] << 16) | ((uint32_t)c.p[1] << 8) | c.p[2]);
-        });
-        break;
-    }
-}
 
 // The cells of rows r0 .. r0 + R - 1 of one source.  R == 4 (r0 a multiple of 4): an integer column
 // loads as one dword / 8 / 16 / 2 x 16 bytes that stay inside the column and are aligned: its capacity
@@ -379,9 +208,7 @@ __global__ __launch_bounds__(OUT_THREADS) void k_output_size(const OutPlan P) {
 // tile's first offset, instead of reading the row's two scanned offsets back.
 template <uint32_t IMG, bool RECOMPUTE>
 __global__ __launch_bounds__(OUT_THREADS) void k_output_pack(const OutPlan P) {
-    // image byte i of a group lies at img[mis + i], mis the group's first output address mod 16: a
-    // 16-byte aligned run of the image is a 16-byte aligned run of the output
-    __shared__ __attribute__((aligned(16))) uint8_t images[OUT_WAVES][IMG + 16];
+    __shared__ __attribute__((aligned(16))) uint8_t images[OUT_WAVES][IMG + 16];  // pack_tile's, one per wave
     const uint32_t lane = threadIdx.x & 63u;
     uint8_t *const img = images[threadIdx.x >> 6];
     const uint32_t tiles = (P.n_rows + 63u) / 64u;
@@ -408,43 +235,10 @@ __global__ __launch_bounds__(OUT_THREADS) void k_output_pack(const OutPlan P) {
             rel0 = (uint32_t)(a - base);
             rel1 = (uint32_t)(b - base);
         }
-        const unsigned long long o0 = base + rel0, o1 = base + rel1;
-        for (uint32_t g0 = 0; g0 < nt;) {
-            // the rows [g0, g1) whose bytes fit the image together
-            const uint32_t gb = __shfl(rel0, g0, 64);
-            const bool fits = lane >= g0 && lane < nt && rel1 - gb <= IMG;
-            const unsigned long long rest = ~__ballot(fits) >> g0;
-            const uint32_t cnt = rest ? (uint32_t)__ffsll((long long)rest) - 1u : 64u - g0;
-            if (!cnt) {  // row g0 alone is longer than the image: straight to the output
-                if (lane == g0 && o1 <= P.total) {
-                    PutW w[1] = {{P.out + o0, P.out + o1}};
-                    encode_rows<1>(P, row, 1u, w, &err);
-                }
-                ++g0;
-                continue;
-            }
-            const uint32_t g1 = g0 + cnt;
-            const uint32_t len = (uint32_t)__shfl(rel1, g1 - 1, 64) - gb;
-            uint8_t *const dst = P.out + base + gb;
-            const uint32_t mis = (uint32_t)((uintptr_t)dst & 15u);
-            if (lane >= g0 && lane < g1 && rel1 > rel0) {
-                PutW w[1] = {{img + mis + (rel0 - gb), img + mis + (rel1 - gb)}};
-                encode_rows<1>(P, row, 1u, w, &err);
-            }
-            __threadfence_block();
-            __builtin_amdgcn_wave_barrier();
-            if (base + gb + len <= P.total) {  // nothing is written past offsets[n_rows]
-                const uint32_t head = min(len, (16u - mis) & 15u);  // ragged head, then tail, then the aligned middle
-                const uint32_t n16 = (len - head) / 16u, tail0 = head + 16u * n16;
-                if (lane < head) dst[lane] = img[mis + lane];
-                if (lane < len - tail0) dst[tail0 + lane] = img[mis + tail0 + lane];
-                for (uint32_t i = lane; i < n16; i += 64u)
-                    *(uint4 *)(dst + head + 16u * i) = *(const uint4 *)(img + mis + head + 16u * i);
-            }
-            __threadfence_block();
-            __builtin_amdgcn_wave_barrier();
-            g0 = g1;
-        }
+        pack_tile<IMG>(lane, nt, base, rel0, rel1, P.out, P.total, img, [&](PutW &pw) {
+            PutW w[1] = {pw};
+            encode_rows<1>(P, row, 1u, w, &err);
+        });
     }
     if (err) atomicOr((unsigned int *)&P.counters[C_ERR], err);
 }

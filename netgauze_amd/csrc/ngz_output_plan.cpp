@@ -125,7 +125,7 @@ Refusal ref_encoding(const IeRow &r, uint8_t transform, uint8_t *enc) {
     return {NGZ_OK, ""};
 }
 
-Refusal build_field(const ngz_output_field &in, CfgField *f) {
+Refusal build_field(const ngz_output_field &in, CfgField *f, bool timestamp_string) {
     if (!in.name || !in.name[0]) return {NGZ_E_INVALID, "a field without a name"};
     f->name = in.name;
     if (f->name.size() > NGZ_OUTPUT_MAX_NAME) return {NGZ_E_LIMIT, "a name longer than 128 bytes"};
@@ -144,7 +144,9 @@ Refusal build_field(const ngz_output_field &in, CfgField *f) {
     }
     if ((in.select == NGZ_OUT_SEL_SINGLE || in.select == NGZ_OUT_SEL_L2SEGMENT) && in.n_refs != 1)
         return {NGZ_E_INVALID, "Single and Layer2SegmentId select one IE"};
-    if (in.transform > NGZ_OUT_TR_MPLS_INDEX) return {NGZ_OUTPUT_E_UNSUPPORTED, "only the Identity, String and MplsIndex transforms are built"};
+    const bool ts = timestamp_string && in.transform == NGZ_OUT_TR_TIMESTAMP_MILLIS_STRING;
+    if (in.transform > NGZ_OUT_TR_MPLS_INDEX && !ts)
+        return {NGZ_OUTPUT_E_UNSUPPORTED, "only the Identity, String and MplsIndex transforms are built"};
     // validate_select_transform_compatibility (:283-367)
     const bool multi = in.select == NGZ_OUT_SEL_MULTI, agg = in.transform == NGZ_OUT_TR_MPLS_INDEX;
     if (multi && !agg) return {NGZ_OUTPUT_E_CONFIG, "Multi selection requires an aggregating transform"};
@@ -169,6 +171,9 @@ Refusal build_field(const ngz_output_field &in, CfgField *f) {
             ref.mpls_n = mpls_index_n(ref.pen, ref.ie);
             ref.enc = ENC_MPLS_ITEM;
             if (!ref.mpls_n) return {NGZ_OUTPUT_E_CONFIG, "MplsIndex requires MPLS label stack fields"};
+        } else if (ts) {  // validate_ie_compatibility (:371-385); then ts.timestamp().to_string() (:934-940)
+            if (!is_datetime(*rows[i])) return {NGZ_OUTPUT_E_CONFIG, "TimestampMillisString requires timestamp IE"};
+            ref.enc = ENC_TS_SECS;
         } else {
             const Refusal r = ref_encoding(*rows[i], in.transform, &ref.enc);
             if (r.rc) return r;
@@ -177,7 +182,7 @@ Refusal build_field(const ngz_output_field &in, CfgField *f) {
     }
     // avro_type (:528-530)
     if (agg) f->avro = NGZ_OUT_T_ARRAY;
-    else if (in.transform == NGZ_OUT_TR_STRING) f->avro = NGZ_OUT_T_STRING;
+    else if (in.transform == NGZ_OUT_TR_STRING || ts) f->avro = NGZ_OUT_T_STRING;
     else if (in.select == NGZ_OUT_SEL_L2SEGMENT) f->avro = NGZ_OUT_T_LONG;
     else f->avro = ie_avro_type(*rows[0]);
     if (in.select == NGZ_OUT_SEL_L2SEGMENT) {
@@ -223,7 +228,7 @@ void put_long(std::vector<uint8_t> &out, int64_t v) {
     out.push_back((uint8_t)z);
 }
 
-int build_config(const ngz_output_field *fields, uint32_t n, Config *cfg, std::string *err) {
+int build_config(const ngz_output_field *fields, uint32_t n, Config *cfg, std::string *err, bool timestamp_string) {
     cfg->fields.clear();
     if (n && !fields) return NGZ_E_INVALID;
     if (n > NGZ_OUTPUT_MAX_FIELDS) {
@@ -233,7 +238,7 @@ int build_config(const ngz_output_field *fields, uint32_t n, Config *cfg, std::s
     std::set<std::string> names;
     for (uint32_t i = 0; i < n; ++i) {
         CfgField f;
-        Refusal r = build_field(fields[i], &f);
+        Refusal r = build_field(fields[i], &f, timestamp_string);
         if (!r.rc && !names.insert(f.name).second) r = {NGZ_E_INVALID, "a field name given twice"};
         if (r.rc) {
             *err = "Invalid FieldConfig for " + (fields[i].name ? std::string(fields[i].name) : "field " + std::to_string(i)) +

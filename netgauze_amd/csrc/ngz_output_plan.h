@@ -27,6 +27,8 @@ enum Enc : uint8_t {
     ENC_DEC_S,       // decimal text of a signed integer
     ENC_BOOLSTR,     // "true" / "false"
     ENC_MPLS_ITEM,   // "{n}-{label}" inside an MplsIndex array
+    ENC_TS_SECS,     // TimestampMillisString: the decimal text of a dateTime's whole seconds (aggregated
+                     // rows only, flow_agg_output.h; its reader hands the seconds on as ENC_DEC_S)
 };
 
 struct CfgRef {
@@ -60,8 +62,9 @@ struct TField {  // one field specifier of a template, scope fields first
 void put_long(std::vector<uint8_t> &out, int64_t v);
 
 // NGZ_OK, or NGZ_OUTPUT_E_UNSUPPORTED / NGZ_OUTPUT_E_CONFIG / NGZ_E_LIMIT / NGZ_E_INVALID with *err
-// naming the field
-int build_config(const ngz_output_field *fields, uint32_t n, Config *cfg, std::string *err);
+// naming the field.  timestamp_string: TimestampMillisString on the dateTime IEs is accepted (the
+// aggregated rows' stage); the column stage refuses it with every other unbuilt transform
+int build_config(const ngz_output_field *fields, uint32_t n, Config *cfg, std::string *err, bool timestamp_string = false);
 
 // get_avro_schema's text
 std::string schema_text(const Config &cfg);

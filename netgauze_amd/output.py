@@ -6,6 +6,10 @@
 `slot(s)` copies one slot's datums to the host; `schema` is get_avro_schema's text; `template_plan` is
 the part of the selects a template alone decides, without a device.
 
+`AggFlowOutput(fields)` is the same config over aggregated groups (include/ngz/flow_agg_output.h): what
+the reference's Avro publisher sends.  `encode(aggregator, raw)` takes the rows `FlowAggregator.flush_raw()`
+/ `emit_raw()` just returned; TimestampMillisString is accepted there on the dateTime IEs.
+
 A field is a dict: {"name", "select": "Single" | "Coalesce" | "Multi" | "Layer2SegmentId", "refs":
 [(pen, ie_id, index)], "transform": "Identity" | "String" | "MplsIndex" | ..., "default": None |
 (RawValue kind, value) such as ("U32", 7) or ("String", "n/a"), "encap": the Layer2SegmentId's
@@ -160,3 +164,75 @@ class FlowOutput:
         a, b = ctypes.c_float(), ctypes.c_float()
         lib().ngz_output_last_timing(self._h, ctypes.byref(a), ctypes.byref(b))
         return a.value, b.value
+
+
+class AggFlowOutput:
+    """One validated FlowOutputConfig over the groups of a FlowAggregator (ngz_agg_output)."""
+
+    def __init__(self, fields, device=0):
+        arr, keep = _c_fields(fields)
+        h, err = ctypes.c_void_p(), ctypes.create_string_buffer(512)
+        rc = lib().ngz_agg_output_create(device, arr, len(fields), ctypes.byref(h), err, len(err))
+        del keep
+        if rc != 0:
+            raise OutputError(err.value.decode() or "ngz_agg_output_create failed (%d)" % rc, rc)
+        self._h = h
+        self.device = device
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            lib().ngz_agg_output_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        if sys.is_finalizing():  # the HIP runtime may be torn down already: leave it to the process exit
+            return
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, rc):
+        if rc < 0:
+            raise OutputError("%s (%d)" % (lib().ngz_agg_output_last_error(self._h).decode(), rc), rc)
+        return rc
+
+    def schema(self):
+        n = int(lib().ngz_agg_output_schema(self._h, None, 0))
+        buf = ctypes.create_string_buffer(n + 1)
+        lib().ngz_agg_output_schema(self._h, buf, n + 1)
+        return buf.value.decode()
+
+    def encode(self, aggregator, raw, stream=None):
+        """Encode the rows `raw` ([n, row_bytes] uint8) that the aggregator's LAST flush_raw / emit_raw
+        returned; this encode's counters."""
+        raw = np.ascontiguousarray(raw, dtype=np.uint8)
+        st = _lib.AggOutputStats()
+        self._check(lib().ngz_agg_output_encode(self._h, aggregator._h, raw.ctypes.data if len(raw) else None, len(raw),
+                                                ctypes.byref(st), ctypes.c_void_p(stream) if stream else None))
+        return st.as_dict()
+
+    def result_pointers(self):
+        """(device pointer of the datums, device pointer of the u64 offsets, rows, bytes) of the last encode."""
+        b, o, n, nb = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_uint64(), ctypes.c_uint64()
+        self._check(lib().ngz_agg_output_result(self._h, ctypes.byref(b), ctypes.byref(o), ctypes.byref(n), ctypes.byref(nb)))
+        return b.value, o.value, int(n.value), int(nb.value)
+
+    def result(self, guard=False):
+        """The last encode on the host: (datums as bytes, offsets as a uint64 array of rows + 1); with
+        `guard` the guard bytes the stage keeps after the datums follow them."""
+        _b, _o, n, nb = self.result_pointers()
+        data = np.empty(nb + (_lib.NGZ_OUTPUT_GUARD if guard else 0), dtype=np.uint8)
+        offs = np.zeros(n + 1, dtype=np.uint64)
+        self._check(lib().ngz_agg_output_to_host(self._h, data.ctypes.data, data.size, offs.ctypes.data, offs.size))
+        return data.tobytes(), offs
+
+    def last_ms(self):
+        """(upload, size pass with its scan, pack pass) of the last encode, device milliseconds."""
+        t = [ctypes.c_float() for _ in range(3)]
+        lib().ngz_agg_output_last_timing(self._h, *[ctypes.byref(x) for x in t])
+        return tuple(x.value for x in t)
+
+    @property
+    def last_launches(self):
+        return int(lib().ngz_agg_output_last_launches(self._h))
