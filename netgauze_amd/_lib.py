@@ -120,6 +120,13 @@ AGG_OUTPUT_FUNCTIONS = [
     "ngz_agg_output_last_timing", "ngz_agg_output_last_launches",
 ]
 NGZ_AGG_OUTPUT_ABI_VERSION = 1
+# include/ngz/flow_agg_json.h
+AGG_JSON_FUNCTIONS = [
+    "ngz_agg_json_abi_version", "ngz_agg_json_create", "ngz_agg_json_destroy", "ngz_agg_json_last_error", "ngz_agg_json_set_option",
+    "ngz_agg_json_encode", "ngz_agg_json_result", "ngz_agg_json_to_host", "ngz_agg_json_last_timing", "ngz_agg_json_last_launches",
+]
+NGZ_AGG_JSON_ABI_VERSION = 1
+NGZ_AGG_JSON_OPT_WRITER = 1
 NGZ_ENRICH_MAX_SCOPE_FIELDS, NGZ_ENRICH_MAX_SHAPES, NGZ_ENRICH_MAX_COLUMNS = 4, 8, 32
 NGZ_ENRICH_MAX_KEY_BYTES, NGZ_ENRICH_MAX_DOMAINS = 16, 253
 NGZ_RENORM_OPTIONS = 0x100
@@ -705,6 +712,29 @@ def load():
     lib.ngz_agg_output_last_timing.restype = I
     lib.ngz_agg_output_last_launches.argtypes = [P]
     lib.ngz_agg_output_last_launches.restype = I
+    # serde JSON of aggregated groups (flow_agg_json.h; ngz_agg_json_stats is laid out as ngz_agg_output_stats)
+    lib.ngz_agg_json_abi_version.argtypes, lib.ngz_agg_json_abi_version.restype = [], I
+    if lib.ngz_agg_json_abi_version() != NGZ_AGG_JSON_ABI_VERSION:
+        raise RuntimeError("netgauze_amd: %s has aggregated-JSON ABI version %d, this binding needs %d -- rebuild it"
+                           % (LIB_PATH, lib.ngz_agg_json_abi_version(), NGZ_AGG_JSON_ABI_VERSION))
+    lib.ngz_agg_json_create.argtypes = [I, ctypes.POINTER(P)]
+    lib.ngz_agg_json_create.restype = I
+    lib.ngz_agg_json_destroy.argtypes = [P]
+    lib.ngz_agg_json_destroy.restype = None
+    lib.ngz_agg_json_last_error.argtypes = [P]
+    lib.ngz_agg_json_last_error.restype = ctypes.c_char_p
+    lib.ngz_agg_json_set_option.argtypes = [P, I, ctypes.c_int64]
+    lib.ngz_agg_json_set_option.restype = I
+    lib.ngz_agg_json_encode.argtypes = [P, P, P, U64, U32, U32, ctypes.c_int64, ctypes.POINTER(AggOutputStats), P]
+    lib.ngz_agg_json_encode.restype = I
+    lib.ngz_agg_json_result.argtypes = [P, ctypes.POINTER(P), ctypes.POINTER(P), ctypes.POINTER(U64), ctypes.POINTER(U64)]
+    lib.ngz_agg_json_result.restype = I
+    lib.ngz_agg_json_to_host.argtypes = [P, P, U64, P, U64]
+    lib.ngz_agg_json_to_host.restype = I
+    lib.ngz_agg_json_last_timing.argtypes = [P] + [ctypes.POINTER(ctypes.c_float)] * 3
+    lib.ngz_agg_json_last_timing.restype = I
+    lib.ngz_agg_json_last_launches.argtypes = [P]
+    lib.ngz_agg_json_last_launches.restype = I
     # ingest (flow_ingest.h)
     lib.ngz_pcap_open.argtypes = [ctypes.c_char_p, ctypes.POINTER(P)]
     lib.ngz_pcap_open.restype = I

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "ngz/flow_agg_output.h"
+#include "ngz_agg_rows.h"
 #include "ngz_host.h"
 #include "ngz_output_enc.h"
 #include "ngz_output_plan.h"
@@ -27,26 +28,18 @@
 namespace {
 
 using namespace ngzenc;
+using namespace ngzrow;
 
 constexpr uint32_t AO_THREADS = 128;
 constexpr uint32_t AO_WAVES = AO_THREADS / 64;
-// Rows are array-of-structures: a lane reads its own row, so in LDS a row takes row_bytes + 4: with a
-// stride of an odd number of dwords the 64 lanes' reads of one field fall into 64 different banks (at
-// a stride of 128 or 256 bytes they would all hit one).  A tile is the rows a wave stages at once: 64
+// A tile is the rows a wave stages at once (ngz_agg_rows.h: a row takes row_bytes + AO_PAD there): 64
 // of 128-byte rows in AO_STAGE_SMALL, 64 of 256-byte rows in AO_STAGE_LARGE, fewer (a multiple of
 // four) of longer rows.
-constexpr uint32_t AO_PAD = 4;
 constexpr uint32_t AO_STAGE_SMALL = 64 * (128 + AO_PAD), AO_STAGE_LARGE = 64 * (256 + AO_PAD);
 constexpr uint32_t AO_IMG = 8176;  // a wave's image, and 16 of slack for the output's misalignment
 constexpr uint32_t AO_DEFAULT_POOL = 1024;
 constexpr uint32_t AO_MAX_REFS = NGZ_OUTPUT_MAX_FIELDS * NGZ_OUTPUT_MAX_REFS;
-constexpr uint32_t BVAL_INLINE = 32;  // bytes of a byte value a row holds (flow_aggregate.h, kkind 3)
 constexpr uint32_t ERR_PEER = 1, ERR_TAIL = 2;
-
-// ngz_agg_row offsets
-constexpr uint32_t R_WINDOW = 0, R_PEER = 6, R_KEYP = 8, R_VALP = 12, R_COUNT = 16, R_MIN_EXPORT = 24, R_MAX_EXPORT = 28,
-                   R_TAKE = 36, R_MAX_COLL = 48, R_TEMPLATES = 56, R_PORTS = 64, R_DOMAINS = 72;
-static_assert(sizeof(ngz_agg_row) == 88 && offsetof(ngz_agg_row, take_id) == R_TAKE && offsetof(ngz_agg_row, domain_bits) == R_DOMAINS, "");
 
 enum : uint8_t { A_KEY, A_VAL, A_ALWAYS, A_PEER4, A_PEER6, A_PORTS, A_DOMAINS, A_TEMPLATES };  // where a candidate lives
 enum : uint8_t { LD_INT, LD_PTR, LD_STRZ, LD_BVAL, LD_WEND };  // how its value is read
@@ -77,9 +70,7 @@ struct AField {
     uint8_t def_len;
     uint8_t l2_encap;
 };
-struct ASetEntry {
-    uint32_t value, bit;
-};
+using ASetEntry = ngzrow::SetEntry;
 // One encode's plan, in device memory (uploaded with the rows): every lane reads it uniformly
 struct APlan {
     ASource src[NGZ_AGG_OUTPUT_MAX_SOURCES];
@@ -104,30 +95,6 @@ struct AArgs {  // passed by value
     unsigned long long total;
     unsigned int *err;
 };
-
-__device__ __forceinline__ uint64_t ld_le(const uint8_t *p, uint32_t w) {  // p: 4-byte aligned for w >= 4
-    if (w == 8) return (uint64_t)*(const uint32_t *)p | ((uint64_t)*(const uint32_t *)(p + 4) << 32);
-    if (w == 4) return *(const uint32_t *)p;
-    return w == 2 ? (uint32_t)p[0] | ((uint32_t)p[1] << 8) : p[0];
-}
-__device__ __forceinline__ int64_t floor_div(int64_t a, int64_t b) {
-    const int64_t q = a / b;
-    return q * b > a ? q - 1 : q;
-}
-
-// The wave's tile of rows into its stage: 16-byte global loads over the contiguous rows, the lanes
-// consecutive; row r at stage + r * (row_bytes + AO_PAD)
-__device__ __forceinline__ void stage_rows(const AArgs &A, uint32_t row0, uint32_t nt, uint8_t *stage, uint32_t lane) {
-    const uint4 *g = (const uint4 *)(A.rows + (uint64_t)row0 * A.row_bytes);
-    const uint32_t per_row = A.row_bytes / 16u, n16 = nt * per_row;
-    for (uint32_t i = lane; i < n16; i += 64u) {
-        const uint4 v = g[i];
-        uint32_t *d = (uint32_t *)(stage + (i / per_row) * (A.row_bytes + AO_PAD) + (i % per_row) * 16u);
-        d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
-    }
-    __threadfence_block();
-    __builtin_amdgcn_wave_barrier();
-}
 
 // The value of candidate S (member m of a set) of row R into c; S.enc / S.width as the encoders want them
 __device__ __forceinline__ void load_value(const APlan &P, const AArgs &A, const uint8_t *R, ASource &S, uint32_t member, Cell &c, uint32_t *err) {
@@ -275,7 +242,7 @@ __global__ __launch_bounds__(AO_THREADS) void k_agg_output_size(const AArgs A) {
     if (blockIdx.x == 0 && threadIdx.x == 0) A.lens[(A.n_rows + 3u) & ~3u] = 0;  // the scan's last item
     for (uint32_t tile = blockIdx.x * AO_WAVES + (threadIdx.x >> 6); tile < tiles; tile += gridDim.x * AO_WAVES) {
         const uint32_t row0 = tile * T, nt = min(T, A.n_rows - row0);
-        stage_rows(A, row0, nt, stage, lane);
+        stage_rows(A.rows, A.row_bytes, row0, nt, stage, lane);
         CountW w;
         if (lane < nt) encode_row(P, A, stage + lane * (A.row_bytes + AO_PAD), w, &err);
         // four lengths per 16-byte store: T and row0 are multiples of four, rows past n_rows count 0
@@ -299,7 +266,7 @@ __global__ __launch_bounds__(AO_THREADS) void k_agg_output_pack(const AArgs A) {
     uint32_t err = 0;
     for (uint32_t tile = blockIdx.x * AO_WAVES + (threadIdx.x >> 6); tile < tiles; tile += gridDim.x * AO_WAVES) {
         const uint32_t row0 = tile * T, nt = min(T, A.n_rows - row0);
-        stage_rows(A, row0, nt, stage, lane);
+        stage_rows(A.rows, A.row_bytes, row0, nt, stage, lane);
         const uint8_t *const R = stage + lane * (A.row_bytes + AO_PAD);
         const unsigned long long a = A.offs[lane < nt ? row0 + lane : A.n_rows], b = lane < nt ? A.offs[row0 + lane + 1] : a;
         const unsigned long long base = __shfl(a, 0, 64);
@@ -430,17 +397,6 @@ bool extra_rule(const Item &it, uint8_t enc, ASource *s) {
     s->ts = TS_NONE;
     return enc == ENC_INT_U || enc == ENC_DEC_U;  // the sets: u16 ports and template ids, u32 domains
 }
-
-uint32_t sorted_set(const std::vector<int64_t> &dict, uint32_t mask, ASetEntry *out, uint32_t cap) {
-    std::vector<ASetEntry> e;
-    for (uint32_t i = 0; i < dict.size() && i < cap; ++i)
-        if (dict[i] >= 0) e.push_back(ASetEntry{(uint32_t)dict[i] & mask, i});
-    std::sort(e.begin(), e.end(), [](const ASetEntry &a, const ASetEntry &b) { return a.value != b.value ? a.value < b.value : a.bit < b.bit; });
-    std::copy(e.begin(), e.end(), out);
-    return (uint32_t)e.size();
-}
-
-constexpr uint64_t align256(uint64_t x) { return (x + 255) & ~255ull; }
 
 }  // namespace
 

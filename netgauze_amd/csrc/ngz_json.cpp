@@ -21,6 +21,7 @@
 
 #include "ngz_host.h"
 #include "ngz_renorm_internal.h"
+#include "ngz_subreg.h"
 
 using namespace ngzh;
 
@@ -506,6 +507,24 @@ int json_render_mode(ngz_ctx *ctx, const JsonView &v, uint32_t d, std::string &o
 int subreg_kind(uint32_t pen, uint16_t id) {
     const SubReg *r = subreg_find(pen, id);
     return r ? (r->nested ? 2 : 1) : 0;
+}
+
+int subreg_names(uint32_t pen, uint16_t id, std::vector<SubregName> *values, std::vector<const char *> *groups) {
+    values->clear();
+    groups->clear();
+    const SubReg *r = subreg_find(pen, id);
+    if (!r) return 0;
+    auto take = [&](uint32_t first, uint32_t count) {
+        for (uint32_t i = first; i < first + count; ++i) values->push_back(SubregName{kSubVals[i].v, kSubVals[i].name});
+    };
+    if (!r->nested) take(r->first, r->count);
+    for (uint32_t g = 0; r->nested && g < r->count; ++g) {
+        groups->push_back(kSubGroups[r->first + g].name);
+        take(kSubGroups[r->first + g].first, kSubGroups[r->first + g].count);
+    }
+    // put_subreg takes the first entry of a value: a stable sort keeps it first
+    std::stable_sort(values->begin(), values->end(), [](const SubregName &a, const SubregName &b) { return a.value < b.value; });
+    return r->nested ? 2 : 1;
 }
 
 // Rank of the values 0..255 of a nested sub-registry (forwardingStatus) in the derived Ord of its

@@ -190,8 +190,9 @@ __device__ __forceinline__ void encode_value(W &w, const S &src, const Cell &c) 
 // their output range (image byte i of a group lies at img[mis + i], mis the group's first output address
 // mod 16: a 16-byte aligned run of the image is a 16-byte aligned run of the output), and copies it out
 // in 16-byte stores; a row longer than the image goes straight out.  encode(w) writes the calling lane's
-// row into the PutW w.  Every lane of the wave calls it; nothing is written at or past out + total.
-template <uint32_t IMG, class Encode>
+// row into the writer w: a WImg{begin, end} over the image, a WOut{begin, end} over the output for a row
+// that goes straight out.  Every lane of the wave calls it; nothing is written at or past out + total.
+template <uint32_t IMG, class WImg = PutW, class WOut = PutW, class Encode>
 __device__ __forceinline__ void pack_tile(uint32_t lane, uint32_t nt, unsigned long long base, uint32_t rel0, uint32_t rel1, uint8_t *out,
                                           unsigned long long total, uint8_t *img, Encode &&encode) {
     const unsigned long long o0 = base + rel0, o1 = base + rel1;
@@ -202,7 +203,7 @@ __device__ __forceinline__ void pack_tile(uint32_t lane, uint32_t nt, unsigned l
         const uint32_t cnt = rest ? (uint32_t)__ffsll((long long)rest) - 1u : 64u - g0;
         if (!cnt) {  // row g0 alone is longer than the image
             if (lane == g0 && o1 <= total) {
-                PutW w{out + o0, out + o1};
+                WOut w{out + o0, out + o1};
                 encode(w);
             }
             ++g0;
@@ -213,7 +214,7 @@ __device__ __forceinline__ void pack_tile(uint32_t lane, uint32_t nt, unsigned l
         uint8_t *const dst = out + base + gb;
         const uint32_t mis = (uint32_t)((uintptr_t)dst & 15u);
         if (lane >= g0 && lane < g1 && rel1 > rel0) {
-            PutW w{img + mis + (rel0 - gb), img + mis + (rel1 - gb)};
+            WImg w{img + mis + (rel0 - gb), img + mis + (rel1 - gb)};
             encode(w);
         }
         __threadfence_block();

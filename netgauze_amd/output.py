@@ -10,6 +10,9 @@ the part of the selects a template alone decides, without a device.
 the reference's Avro publisher sends.  `encode(aggregator, raw)` takes the rows `FlowAggregator.flush_raw()`
 / `emit_raw()` just returned; TimestampMillisString is accepted there on the dateTime IEs.
 
+`AggFlowJson()` is the JSON publisher over the same rows (include/ngz/flow_agg_json.h): `encode(aggregator,
+raw, shard_id, seq0, export_time_ms)` renders on the device the lines `FlowAggregator.flowinfo_json` gives.
+
 A field is a dict: {"name", "select": "Single" | "Coalesce" | "Multi" | "Layer2SegmentId", "refs":
 [(pen, ie_id, index)], "transform": "Identity" | "String" | "MplsIndex" | ..., "default": None |
 (RawValue kind, value) such as ("U32", 7) or ("String", "n/a"), "encap": the Layer2SegmentId's
@@ -236,3 +239,72 @@ class AggFlowOutput:
     @property
     def last_launches(self):
         return int(lib().ngz_agg_output_last_launches(self._h))
+
+
+class AggFlowJson:
+    """The serde JSON lines of the groups of a FlowAggregator, rendered on the device (ngz_agg_json)."""
+
+    def __init__(self, device=0):
+        h = ctypes.c_void_p()
+        rc = lib().ngz_agg_json_create(device, ctypes.byref(h))
+        if rc != 0:
+            raise OutputError("ngz_agg_json_create failed (%d)" % rc, rc)
+        self._h = h
+        self.device = device
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            lib().ngz_agg_json_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        if sys.is_finalizing():  # the HIP runtime may be torn down already: leave it to the process exit
+            return
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, rc):
+        if rc < 0:
+            raise OutputError("%s (%d)" % (lib().ngz_agg_json_last_error(self._h).decode(), rc), rc)
+        return rc
+
+    def set_option(self, opt, value):
+        """ngz_agg_json_set_option: NGZ_AGG_JSON_OPT_WRITER 0 accumulating | 1 byte writer (how the pack pass
+        runs, never what it writes)."""
+        self._check(lib().ngz_agg_json_set_option(self._h, opt, value))
+
+    def encode(self, aggregator, raw, shard_id=0, seq0=0, export_time_ms=0, stream=None):
+        """Render the rows `raw` ([n, row_bytes] uint8) that the aggregator's LAST flush_raw / emit_raw
+        returned, with the packet header of FlowAggregator.flowinfo_json; this encode's counters."""
+        raw = np.ascontiguousarray(raw, dtype=np.uint8)
+        st = _lib.AggOutputStats()
+        self._check(lib().ngz_agg_json_encode(self._h, aggregator._h, raw.ctypes.data if len(raw) else None, len(raw), shard_id, seq0,
+                                              export_time_ms, ctypes.byref(st), ctypes.c_void_p(stream) if stream else None))
+        return st.as_dict()
+
+    def result_pointers(self):
+        """(device pointer of the lines, device pointer of the u64 offsets, rows, bytes) of the last encode."""
+        b, o, n, nb = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_uint64(), ctypes.c_uint64()
+        self._check(lib().ngz_agg_json_result(self._h, ctypes.byref(b), ctypes.byref(o), ctypes.byref(n), ctypes.byref(nb)))
+        return b.value, o.value, int(n.value), int(nb.value)
+
+    def result(self, guard=False):
+        """The last encode on the host: (lines back to back as bytes, offsets as a uint64 array of rows + 1);
+        with `guard` the guard bytes the stage keeps after the lines follow them."""
+        _b, _o, n, nb = self.result_pointers()
+        data = np.empty(nb + (_lib.NGZ_OUTPUT_GUARD if guard else 0), dtype=np.uint8)
+        offs = np.zeros(n + 1, dtype=np.uint64)
+        self._check(lib().ngz_agg_json_to_host(self._h, data.ctypes.data, data.size, offs.ctypes.data, offs.size))
+        return data.tobytes(), offs
+
+    def last_ms(self):
+        """(upload, size pass with its scan, pack pass) of the last encode, device milliseconds."""
+        t = [ctypes.c_float() for _ in range(3)]
+        lib().ngz_agg_json_last_timing(self._h, *[ctypes.byref(x) for x in t])
+        return tuple(x.value for x in t)
+
+    @property
+    def last_launches(self):
+        return int(lib().ngz_agg_json_last_launches(self._h))
