@@ -127,6 +127,13 @@ AGG_JSON_FUNCTIONS = [
 ]
 NGZ_AGG_JSON_ABI_VERSION = 1
 NGZ_AGG_JSON_OPT_WRITER = 1
+# include/ngz/flow_json.h
+FLOW_JSON_FUNCTIONS = [
+    "ngz_flow_json_abi_version", "ngz_flow_json_create", "ngz_flow_json_destroy", "ngz_flow_json_last_error", "ngz_flow_json_encode",
+    "ngz_flow_json_result", "ngz_flow_json_to_host", "ngz_flow_json_last_timing", "ngz_flow_json_last_launches",
+]
+NGZ_FLOW_JSON_ABI_VERSION = 1
+NGZ_FLOW_JSON_NONE, NGZ_FLOW_JSON_LINE, NGZ_FLOW_JSON_HOST = 0, 1, 2
 NGZ_ENRICH_MAX_SCOPE_FIELDS, NGZ_ENRICH_MAX_SHAPES, NGZ_ENRICH_MAX_COLUMNS = 4, 8, 32
 NGZ_ENRICH_MAX_KEY_BYTES, NGZ_ENRICH_MAX_DOMAINS = 16, 253
 NGZ_RENORM_OPTIONS = 0x100
@@ -409,6 +416,15 @@ assert (ctypes.sizeof(OutputField), ctypes.sizeof(OutputFieldPlan), ctypes.sizeo
 class AggOutputStats(ctypes.Structure):
     """ngz_agg_output_stats."""
     _fields_ = [("rows", ctypes.c_uint64), ("bytes", ctypes.c_uint64), ("tail_bytes", ctypes.c_uint64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class FlowJsonStats(ctypes.Structure):
+    """ngz_flow_json_stats."""
+    _fields_ = [("lines", ctypes.c_uint64), ("bytes", ctypes.c_uint64), ("left_template", ctypes.c_uint64),
+                ("left_float", ctypes.c_uint64), ("not_ok", ctypes.c_uint64)]
 
     def as_dict(self):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
@@ -735,6 +751,27 @@ def load():
     lib.ngz_agg_json_last_timing.restype = I
     lib.ngz_agg_json_last_launches.argtypes = [P]
     lib.ngz_agg_json_last_launches.restype = I
+    # serde JSON of decoded messages (flow_json.h)
+    lib.ngz_flow_json_abi_version.argtypes, lib.ngz_flow_json_abi_version.restype = [], I
+    if lib.ngz_flow_json_abi_version() != NGZ_FLOW_JSON_ABI_VERSION:
+        raise RuntimeError("netgauze_amd: %s has flow-JSON ABI version %d, this binding needs %d -- rebuild it"
+                           % (LIB_PATH, lib.ngz_flow_json_abi_version(), NGZ_FLOW_JSON_ABI_VERSION))
+    lib.ngz_flow_json_create.argtypes = [I, ctypes.POINTER(P)]
+    lib.ngz_flow_json_create.restype = I
+    lib.ngz_flow_json_destroy.argtypes = [P]
+    lib.ngz_flow_json_destroy.restype = None
+    lib.ngz_flow_json_last_error.argtypes = [P]
+    lib.ngz_flow_json_last_error.restype = ctypes.c_char_p
+    lib.ngz_flow_json_encode.argtypes = [P, P, ctypes.POINTER(BatchOut), ctypes.POINTER(FlowJsonStats), P]
+    lib.ngz_flow_json_encode.restype = I
+    lib.ngz_flow_json_result.argtypes = [P, ctypes.POINTER(P), ctypes.POINTER(P), ctypes.POINTER(P), ctypes.POINTER(U64), ctypes.POINTER(U64)]
+    lib.ngz_flow_json_result.restype = I
+    lib.ngz_flow_json_to_host.argtypes = [P, P, U64, P, U64, P, U64]
+    lib.ngz_flow_json_to_host.restype = I
+    lib.ngz_flow_json_last_timing.argtypes = [P] + [ctypes.POINTER(ctypes.c_float)] * 3
+    lib.ngz_flow_json_last_timing.restype = I
+    lib.ngz_flow_json_last_launches.argtypes = [P]
+    lib.ngz_flow_json_last_launches.restype = I
     # ingest (flow_ingest.h)
     lib.ngz_pcap_open.argtypes = [ctypes.c_char_p, ctypes.POINTER(P)]
     lib.ngz_pcap_open.restype = I

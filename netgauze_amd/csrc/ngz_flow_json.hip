@@ -1,0 +1,717 @@
+// serde JSON of decoded messages (include/ngz/flow_json.h): the line ngz_dgram_json (ngz_json.cpp, the
+// specification) gives for each OK datagram of a batch, rendered on the device from the decoded columns.
+// The whole output is one byte stream in stream order; every byte belongs either to a record (with the
+// comma after it inside its set) or to glue: datagram head, set head, set tail, commas between sets,
+// datagram tail.  The unit of work is a tile: at most 64 consecutive records of one data set.  They are
+// consecutive rows of the slot's columns, so a lane-per-row load coalesces, and consecutive in the output,
+// so a wave's LDS image (pack_tile, ngz_output_enc.h) holds them.  Per encode the host lists every slot's
+// fields as items (column, renderer, separator and tag as constant text in a dword-padded pool), uploads
+// the plan in one copy, and runs, whatever the number of slots,
+//   k_fj_dgrams     one thread per datagram: rendered, not OK, or left to the host for its template sets,
+//   k_fj_sets       one thread per data set: its datagram's range of sets; a float template's datagram
+//                   is left to the host,
+//   k_fj_tiles      one thread per data set: its tiles, ceil(n / 64), if its datagram is rendered,
+//   a hipcub exclusive scan and k_fj_fill: the tile table (set, first record),
+//   k_fj_size       a wave per tile, a lane per record through the counting writer, a wave sum per tile,
+//   k_fj_set_len    one thread per set: head, its tiles, tail,
+//   k_fj_dgram_len  one thread per datagram: head, sets, commas, tail; the stats,
+//   a hipcub exclusive scan: the u64 offsets,
+//   k_fj_glue_dgrams / k_fj_glue_sets  the same two walks downwards: every set's and tile's output offset,
+//                   and the glue itself, written straight out by bytes,
+//   k_fj_pack       a wave per tile: lane l sizes record l again, a wave scan places it, JAcc renders it
+//                   into the wave's LDS image, which goes out in 16-byte stores; a record longer than the
+//                   image goes straight out through the byte writer.
+// pack_tile stores its ragged ends by bytes, so the glue and pack passes write disjoint bytes.
+#include <hip/hip_runtime.h>
+#include <hipcub/hipcub.hpp>
+
+#include <algorithm>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "ngz/flow_json.h"
+#include "ngz_host.h"
+#include "ngz_json_dev.h"
+#include "ngz_output_enc.h"
+#include "ngz_stage.h"
+
+namespace {
+
+using namespace ngzjson;
+using ngzrow::align256;
+
+constexpr uint32_t FJ_THREADS = 256;
+constexpr uint32_t FJ_TILE = 64;
+// A wave's image, and 16 of slack for the output's misalignment: §2i's.  Nothing is staged here (a lane
+// loads its own row's cells from the columns), so a block's LDS is the image: 30 KB, five blocks per CU.
+constexpr uint32_t FJ_IMG = 30704;
+constexpr uint32_t ERR_SETS = 1, ERR_VLEN = 2, ERR_TILES = 4;
+constexpr uint32_t C_ERR = 0, C_LINES = 1, C_TEMPLATE = 2, C_FLOAT = 3, C_NOT_OK = 4, C_COUNT = 5;
+constexpr uint8_t HOW_FLOAT = 3;  // between k_fj_sets and k_fj_dgram_len: NGZ_FLOW_JSON_HOST for a float field
+
+enum : uint8_t {  // put_value / put_field of ngz_json.cpp, case by case
+    RD_NULL, RD_U64, RD_I64, RD_BOOL, RD_IP4, RD_IP6, RD_LIST, RD_STRZ, RD_DT_SECS, RD_DT_MS, RD_DT_FRAC, RD_TCP, RD_SUBREG,
+    RD_SUBREG_NESTED, RD_VSTR, RD_VLIST
+};
+enum { T_V10_A, T_SEQ, T_V10_DOMAIN, T_V9_A, T_V9_TIME, T_V9_SOURCE, T_SETS, T_DGRAM_TAIL, T_SET_TAIL, T_UNASSIGNED, T_COUNT };
+
+struct FItem {
+    const uint8_t *col;  // the field's column: row r at col + r * width
+    JText pre, suf;      // the separator before the field and its tag, around its value
+    uint16_t width;
+    uint8_t rend, reserved;
+    JSub sub;
+};
+struct FSlot {
+    uint32_t item0, n_items;  // its fields in template order, scope fields first
+    uint32_t n_rows, has_float;
+    JText rec_head, rec_tail, set_head;  // {"scope_fields":[  |  ]}  |  {"Data":{"id":<template id>,"records":[
+};
+struct FTile {
+    uint32_t set, first;  // records [first, first + 64) of the set, as far as it has them
+};
+struct FArgs {  // passed by value
+    const FSlot *slots;
+    const FItem *items;
+    const JName *names;
+    const uint32_t *pool;
+    const uint32_t *host_dgrams;  // the datagrams with (options) template sets, ascending
+    JText fixed[T_COUNT];
+    const ngz_set_info *sets;
+    const ngz_dgram_hdr *hdr;
+    const uint8_t *in;  // the batch input
+    unsigned long long in_size;
+    uint32_t n_host, n_sets, n_dgrams, n_slots, tile_cap;
+    uint8_t *how;
+    uint32_t *dset0, *dset1;  // per datagram: its sets [dset0, dset1)
+    uint32_t *ntiles, *tile0;  // per set, and one more: tile0[n_sets] is the number of tiles
+    FTile *tiles;
+    uint32_t *tile_bytes;
+    unsigned long long *tile_off, *set_len, *set_off, *dlen, *offs;
+    uint8_t *out;
+    unsigned long long total;
+    unsigned long long *counters;
+};
+
+__device__ __forceinline__ uint64_t ld_cell(const uint8_t *p, uint32_t w) {  // p: aligned to w
+    return w == 8 ? *(const uint64_t *)p : w == 4 ? *(const uint32_t *)p : w == 2 ? *(const uint16_t *)p : *p;
+}
+
+// A set inside the batch's tables
+__device__ __forceinline__ bool set_ok(const FArgs &A, const ngz_set_info &si) {
+    return si.dgram < A.n_dgrams && si.slot < A.n_slots && (!si.n || (uint64_t)si.rec0 + si.n <= A.slots[si.slot].n_rows);
+}
+
+template <class W>
+__device__ __forceinline__ void render_value(W &w, const FArgs &A, const FItem &it, uint32_t row, uint32_t *err) {
+    const uint8_t *cell = it.col + (uint64_t)row * it.width;
+    switch (it.rend) {
+    case RD_U64: put_dec(w, ld_cell(cell, it.width)); break;
+    case RD_I64: {
+        const int shift = 64 - 8 * (int)it.width;
+        const int64_t sv = (int64_t)(ld_cell(cell, it.width) << shift) >> shift;
+        if (sv < 0) w.push('-', 1);
+        put_dec(w, sv < 0 ? 0ull - (uint64_t)sv : (uint64_t)sv);
+        break;
+    }
+    case RD_BOOL: put_bool(w, cell[0] != 0); break;
+    case RD_IP4: put_ip4_str(w, ld_cell(cell, it.width) & 0xFFFFFFFFu); break;
+    case RD_IP6: put_ip6_str(w, cell); break;
+    case RD_LIST: put_list(w, cell, it.width); break;
+    case RD_STRZ: {  // a fixed string ends at its first NUL
+        uint32_t n = 0;
+        while (n < it.width && cell[n]) ++n;
+        put_str(w, cell, n);
+        break;
+    }
+    case RD_DT_SECS: put_datetime(w, (int64_t)ld_cell(cell, it.width), 0); break;
+    case RD_DT_MS: {
+        const int64_t ms = (int64_t)ld_cell(cell, 8), secs = floor_div(ms, 1000);
+        put_datetime(w, secs, (uint32_t)(ms - secs * 1000) * 1000000u);
+        break;
+    }
+    case RD_DT_FRAC: {  // {u32 secs, u32 nanos}
+        const uint64_t v = ld_cell(cell, 8);
+        put_datetime(w, (int64_t)(uint32_t)v, (uint32_t)(v >> 32));
+        break;
+    }
+    case RD_TCP: put_tcp(w, cell[0]); break;
+    case RD_SUBREG:
+    case RD_SUBREG_NESTED:
+        put_subreg(w, A.names, A.pool, A.fixed[T_UNASSIGNED], it.sub, it.rend == RD_SUBREG_NESTED, ld_cell(cell, it.width));
+        break;
+    case RD_VSTR:
+    case RD_VLIST: {  // {u64 offset into the batch input, u32 length}; outside it: empty, and the encode fails
+        const uint64_t off = *(const uint64_t *)cell;
+        uint32_t len = *(const uint32_t *)(cell + 8);
+        const uint8_t *p = A.in;
+        if (off > A.in_size || len > A.in_size - off) {
+            *err |= ERR_VLEN;
+            len = 0;
+        } else {
+            p += off;
+        }
+        if (it.rend == RD_VSTR) put_str(w, p, len);
+        else put_list(w, p, len);
+        break;
+    }
+    default: w.push('n' | ('u' << 8) | ('l' << 16) | ('l' << 24), 4); break;
+    }
+}
+
+// Row `row` of slot S as a record of its set, and the comma after it unless it is the set's last
+template <class W>
+__device__ __forceinline__ void render_record(const FArgs &A, const FSlot &S, uint32_t row, bool last, W &w, uint32_t *err) {
+    w.text(A.pool + S.rec_head.off / 4u, S.rec_head.len);
+    for (uint32_t i = 0; i < S.n_items; ++i) {
+        const FItem &it = A.items[S.item0 + i];
+        w.text(A.pool + it.pre.off / 4u, it.pre.len);
+        render_value(w, A, it, row, err);
+        w.text(A.pool + it.suf.off / 4u, it.suf.len);
+    }
+    w.text(A.pool + S.rec_tail.off / 4u, S.rec_tail.len);
+    if (!last) w.push(',', 1);
+    w.finish();
+}
+
+// The datagram's text up to its first set
+template <class W>
+__device__ __forceinline__ void render_head(const FArgs &A, const ngz_dgram_hdr &h, W &w) {
+    auto fixed = [&](int t) { w.text(A.pool + A.fixed[t].off / 4u, A.fixed[t].len); };
+    if (h.version == 10) {
+        fixed(T_V10_A);
+        put_datetime(w, (int64_t)h.time, 0);
+        fixed(T_SEQ);
+        put_dec(w, h.sequence);
+        fixed(T_V10_DOMAIN);
+        put_dec(w, h.domain);
+    } else {
+        fixed(T_V9_A);
+        put_dec(w, h.sys_up_time);
+        fixed(T_V9_TIME);
+        put_datetime(w, (int64_t)h.time, 0);
+        fixed(T_SEQ);
+        put_dec(w, h.sequence);
+        fixed(T_V9_SOURCE);
+        put_dec(w, h.domain);
+    }
+    fixed(T_SETS);
+}
+
+// ---------------------------------------------------------------------------------------------
+// kernels
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(FJ_THREADS) void k_fj_dgrams(const FArgs A) {
+    const uint32_t d = blockIdx.x * FJ_THREADS + threadIdx.x;
+    if (d >= A.n_dgrams) return;
+    uint8_t how = A.hdr[d].status == NGZ_DG_OK ? NGZ_FLOW_JSON_LINE : NGZ_FLOW_JSON_NONE;
+    uint32_t lo = 0, hi = A.n_host;
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (A.host_dgrams[mid] < d) lo = mid + 1;
+        else hi = mid;
+    }
+    if (how == NGZ_FLOW_JSON_LINE && lo < A.n_host && A.host_dgrams[lo] == d) how = NGZ_FLOW_JSON_HOST;
+    A.how[d] = how;
+    A.dset0[d] = A.dset1[d] = 0;
+}
+
+__global__ __launch_bounds__(FJ_THREADS) void k_fj_sets(const FArgs A) {
+    const uint32_t s = blockIdx.x * FJ_THREADS + threadIdx.x;
+    if (s >= A.n_sets) return;
+    const ngz_set_info si = A.sets[s];
+    if (!set_ok(A, si)) {
+        atomicOr((unsigned int *)&A.counters[C_ERR], ERR_SETS);
+        return;
+    }
+    if (s == 0 || A.sets[s - 1].dgram != si.dgram) A.dset0[si.dgram] = s;  // the sets are in stream order
+    if (s + 1 == A.n_sets || A.sets[s + 1].dgram != si.dgram) A.dset1[si.dgram] = s + 1;
+    if (A.slots[si.slot].has_float && A.how[si.dgram] == NGZ_FLOW_JSON_LINE) A.how[si.dgram] = HOW_FLOAT;
+}
+
+__global__ __launch_bounds__(FJ_THREADS) void k_fj_tiles(const FArgs A) {
+    const uint32_t s = blockIdx.x * FJ_THREADS + threadIdx.x;
+    if (s > A.n_sets) return;
+    uint32_t n = 0;
+    if (s < A.n_sets) {
+        const ngz_set_info si = A.sets[s];
+        if (set_ok(A, si) && A.how[si.dgram] == NGZ_FLOW_JSON_LINE) n = (si.n + FJ_TILE - 1) / FJ_TILE;
+    }
+    A.ntiles[s] = n;  // ntiles[n_sets] = 0: the scan's last item
+}
+
+__global__ __launch_bounds__(FJ_THREADS) void k_fj_fill(const FArgs A) {
+    const uint32_t s = blockIdx.x * FJ_THREADS + threadIdx.x;
+    if (s >= A.n_sets) return;
+    const uint32_t t0 = A.tile0[s], n = A.ntiles[s];
+    for (uint32_t t = 0; t < n; ++t) {
+        if (t0 + t >= A.tile_cap || t0 + t < t0) {
+            atomicOr((unsigned int *)&A.counters[C_ERR], ERR_TILES);
+            break;
+        }
+        A.tiles[t0 + t] = FTile{s, t * FJ_TILE};
+    }
+}
+
+__global__ __launch_bounds__(FJ_THREADS) void k_fj_size(const FArgs A) {
+    const uint32_t lane = threadIdx.x & 63u, n_tiles = min(A.tile0[A.n_sets], A.tile_cap);
+    uint32_t err = 0;
+    for (uint32_t t = blockIdx.x * (FJ_THREADS / 64u) + (threadIdx.x >> 6); t < n_tiles; t += gridDim.x * (FJ_THREADS / 64u)) {
+        const FTile tl = A.tiles[t];
+        const ngz_set_info si = A.sets[tl.set];
+        const FSlot &S = A.slots[si.slot];
+        const uint32_t cnt = min(FJ_TILE, si.n - tl.first);
+        JCount w;
+        if (lane < cnt) render_record(A, S, si.rec0 + tl.first + lane, tl.first + lane + 1u == si.n, w, &err);
+        const uint64_t sum = ngzs::wave_sum(w.n);
+        if (lane == 0) A.tile_bytes[t] = (uint32_t)sum;
+    }
+    if (err) atomicOr((unsigned int *)&A.counters[C_ERR], err);
+}
+
+__global__ __launch_bounds__(FJ_THREADS) void k_fj_set_len(const FArgs A) {
+    const uint32_t s = blockIdx.x * FJ_THREADS + threadIdx.x;
+    if (s >= A.n_sets) return;
+    const ngz_set_info si = A.sets[s];
+    unsigned long long len = 0;
+    if (set_ok(A, si) && A.how[si.dgram] == NGZ_FLOW_JSON_LINE) {
+        len = A.slots[si.slot].set_head.len + A.fixed[T_SET_TAIL].len;
+        const uint32_t t1 = min(A.tile0[s + 1], A.tile_cap);
+        for (uint32_t t = A.tile0[s]; t < t1; ++t) len += A.tile_bytes[t];
+    }
+    A.set_len[s] = len;
+}
+
+__global__ __launch_bounds__(FJ_THREADS) void k_fj_dgram_len(const FArgs A) {
+    __shared__ unsigned long long acc[4];
+    const uint32_t d = blockIdx.x * FJ_THREADS + threadIdx.x;
+    uint64_t c[4] = {0, 0, 0, 0};  // lines, left for templates, left for floats, not OK
+    if (d < A.n_dgrams) {
+        unsigned long long len = 0;
+        const uint8_t how = A.how[d];
+        if (how == NGZ_FLOW_JSON_LINE) {
+            JCount w;
+            render_head(A, A.hdr[d], w);
+            const uint32_t s0 = A.dset0[d], s1 = min(A.dset1[d], A.n_sets);
+            len = w.n + A.fixed[T_DGRAM_TAIL].len + (s1 > s0 ? s1 - s0 - 1u : 0u);  // a comma between two sets
+            for (uint32_t s = s0; s < s1; ++s) len += A.set_len[s];
+            c[0] = 1;
+        } else if (how == HOW_FLOAT) {
+            A.how[d] = NGZ_FLOW_JSON_HOST;
+            c[2] = 1;
+        } else {
+            c[how == NGZ_FLOW_JSON_HOST ? 1 : 3] = 1;
+        }
+        A.dlen[d] = len;
+        if (d == 0) A.dlen[A.n_dgrams] = 0;  // the scan's last item
+    }
+    unsigned long long *const dst[4] = {&A.counters[C_LINES], &A.counters[C_TEMPLATE], &A.counters[C_FLOAT], &A.counters[C_NOT_OK]};
+    ngzs::block_add<4>(acc, c, dst);
+}
+
+// The datagram's head, the commas between its sets and its closing text; where each of its sets starts
+__global__ __launch_bounds__(FJ_THREADS) void k_fj_glue_dgrams(const FArgs A) {
+    const uint32_t d = blockIdx.x * FJ_THREADS + threadIdx.x;
+    if (d >= A.n_dgrams || A.how[d] != NGZ_FLOW_JSON_LINE) return;
+    const unsigned long long o1 = min(A.offs[d + 1], A.total);
+    JByte w{A.out + A.offs[d], A.out + o1};
+    render_head(A, A.hdr[d], w);
+    const uint32_t s0 = A.dset0[d], s1 = min(A.dset1[d], A.n_sets);
+    for (uint32_t s = s0; s < s1; ++s) {
+        if (s > s0) w.put(',');
+        A.set_off[s] = (unsigned long long)(w.p - A.out);
+        w.p += A.set_len[s];
+    }
+    w.text(A.pool + A.fixed[T_DGRAM_TAIL].off / 4u, A.fixed[T_DGRAM_TAIL].len);
+}
+
+// The set's head and tail; where each of its tiles starts
+__global__ __launch_bounds__(FJ_THREADS) void k_fj_glue_sets(const FArgs A) {
+    const uint32_t s = blockIdx.x * FJ_THREADS + threadIdx.x;
+    if (s >= A.n_sets) return;
+    const ngz_set_info si = A.sets[s];
+    if (A.how[si.dgram] != NGZ_FLOW_JSON_LINE) return;
+    const JText head = A.slots[si.slot].set_head;
+    const unsigned long long o0 = A.set_off[s], o1 = min(o0 + A.set_len[s], A.total);
+    JByte w{A.out + o0, A.out + o1};
+    w.text(A.pool + head.off / 4u, head.len);
+    const uint32_t t1 = min(A.tile0[s + 1], A.tile_cap);
+    for (uint32_t t = A.tile0[s]; t < t1; ++t) {
+        A.tile_off[t] = (unsigned long long)(w.p - A.out);
+        w.p += A.tile_bytes[t];
+    }
+    w.text(A.pool + A.fixed[T_SET_TAIL].off / 4u, A.fixed[T_SET_TAIL].len);
+}
+
+// One wave per block: LDS, not threads, bounds what a CU holds
+template <class WImg>
+__global__ __launch_bounds__(64) void k_fj_pack(const FArgs A, const uint32_t n_tiles) {
+    __shared__ __attribute__((aligned(16))) uint8_t img[FJ_IMG + 16];  // pack_tile's
+    const uint32_t lane = threadIdx.x;
+    uint32_t err = 0;
+    for (uint32_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
+        const FTile tl = A.tiles[t];
+        const ngz_set_info si = A.sets[tl.set];
+        const FSlot &S = A.slots[si.slot];
+        const uint32_t cnt = min(FJ_TILE, si.n - tl.first), row = si.rec0 + tl.first + lane;
+        const bool last = tl.first + lane + 1u == si.n;
+        JCount c;
+        if (lane < cnt) render_record(A, S, row, last, c, &err);
+        uint32_t incl = c.n;
+#pragma unroll
+        for (int k = 1; k < 64; k <<= 1) {
+            const uint32_t up = __shfl_up(incl, k, 64);
+            if (lane >= (uint32_t)k) incl += up;
+        }
+        ngzenc::pack_tile<FJ_IMG, WImg, JByte>(lane, cnt, A.tile_off[t], incl - c.n, incl, A.out, A.total, img,
+                                               [&](auto &w) { render_record(A, S, row, last, w, &err); });
+    }
+    if (err) atomicOr((unsigned int *)&A.counters[C_ERR], err);
+}
+
+}  // namespace
+
+struct ngz_flow_json : ngzs::Stage {
+    ngz_flow_json() : Stage(4) {}
+    float size_ms = 0, offsets_ms = 0, pack_ms = 0;
+    int launches = 0;
+    uint64_t n_dgrams = 0, n_bytes = 0;  // the last encode
+    bool have = false;
+    ngzh::DevBuf<uint8_t> d_in, d_how, d_bytes, d_scan_tmp;  // d_in: slots, items, names, pool, template datagrams
+    ngzh::DevBuf<uint32_t> d_u32;                            // dset0, dset1, ntiles, tile0, tile_bytes
+    ngzh::DevBuf<FTile> d_tiles;
+    ngzh::DevBuf<unsigned long long> d_u64, d_offs, d_counters;  // d_u64: tile_off, set_len, set_off, dlen
+    ngzs::PinnedBuf<uint8_t> h_in;
+    ngzs::PinnedBuf<unsigned long long> h_back;  // the counters, the total, the tiles
+};
+
+namespace {
+
+using ngzh::Spec;
+
+std::string ie_label(const Spec &s) {
+    return s.name ? std::string(s.name) : "pen " + std::to_string(s.pen) + " id " + std::to_string(s.id);
+}
+
+const char *const kScopeNames[] = {nullptr, "System", "Interface", "LineCard", "Cache", "Template"};
+
+// put_field / put_value's choice for field `sp` of column layout `fd`.  *is_float: serde_json's float text,
+// which the device does not render.  false: a column the loaders cannot read.
+bool pick(const Spec &sp, const DevField &fd, Pool &pool, std::vector<JName> &names, FItem *it, std::string *pre, std::string *suf,
+          bool *is_float) {
+    const bool int_w = fd.width == 1 || fd.width == 2 || fd.width == 4 || fd.width == 8;
+    it->width = fd.width;
+    it->rend = RD_NULL;
+    if (sp.kind == ngzh::IK_SCOPE) {  // NFv9 ScopeField: a known scope's u32 or bytes, an unknown one's bytes
+        const char *nm = sp.pen == 0 && sp.id >= 1 && sp.id <= 5 ? kScopeNames[sp.id] : nullptr;
+        if (nm) {
+            *pre = std::string("{\"") + nm + "\":";
+            *suf = "}";
+        } else {
+            *pre = "{\"Unknown\":{\"pen\":" + std::to_string(sp.pen) + ",\"id\":" + std::to_string(sp.id) + ",\"value\":";
+            *suf = "}}";
+        }
+        it->rend = nm && fd.kind == NGZ_K_SCOPE32 ? RD_U64 : RD_LIST;
+        return it->rend == RD_LIST || fd.width == 4;
+    }
+    tag_text(sp, pre, suf);
+    const bool known = sp.kind == ngzh::IK_IANA || sp.kind == ngzh::IK_VENDOR;
+    switch (fd.kind) {
+    case NGZ_K_UINT:
+        it->rend = RD_U64;
+        if (known && (sp.flags & 4)) {
+            if (const int sk = add_subreg(sp.pen, sp.id, pool, names, &it->sub)) {
+                it->rend = sk == 2 ? RD_SUBREG_NESTED : RD_SUBREG;
+                return int_w;
+            }
+        }
+        if (known && (sp.dtype == ngzh::DT_float32 || sp.dtype == ngzh::DT_float64)) *is_float = true;
+        if (known && sp.dtype == ngzh::DT_ipv4Address) it->rend = RD_IP4;
+        if (known && sp.dtype == ngzh::DT_dateTimeSeconds) it->rend = RD_DT_SECS;
+        return int_w;
+    case NGZ_K_SCOPE32: it->rend = RD_U64; return fd.width == 4;
+    case NGZ_K_TCPFLAGS: it->rend = RD_TCP; return true;
+    case NGZ_K_SINT: it->rend = RD_I64; return int_w;
+    case NGZ_K_BOOL: it->rend = RD_BOOL; return true;
+    case NGZ_K_BYTES: it->rend = known && sp.dtype == ngzh::DT_ipv6Address && fd.width == 16 ? RD_IP6 : RD_LIST; return true;
+    case NGZ_K_U256: it->rend = RD_LIST; return fd.width == 32;
+    case NGZ_K_DTMS: it->rend = RD_DT_MS; return fd.width == 8;
+    case NGZ_K_DTFRAC: it->rend = RD_DT_FRAC; return fd.width == 8;
+    case NGZ_K_STR: it->rend = RD_STRZ; return true;
+    case NGZ_K_VLEN: it->rend = (fd.flags & 0x80) ? RD_VSTR : RD_VLIST; return fd.width == 16;
+    }
+    return true;  // a kind put_value prints as null
+}
+
+uint32_t blocks(uint64_t items) { return (uint32_t)((items + FJ_THREADS - 1) / FJ_THREADS); }
+
+}  // namespace
+
+extern "C" {
+
+int ngz_flow_json_abi_version(void) { return NGZ_FLOW_JSON_ABI_VERSION; }
+
+int ngz_flow_json_create(int device, ngz_flow_json **out) {
+    if (!out) return NGZ_E_INVALID;
+    *out = nullptr;
+    if (device < 0) return NGZ_E_INVALID;
+    ngz_flow_json *j = new ngz_flow_json;
+    j->device = device;
+    *out = j;
+    return NGZ_OK;
+}
+
+void ngz_flow_json_destroy(ngz_flow_json *j) {
+    if (!j) return;
+    if (j->device_ready) {
+        hipSetDevice(j->device);
+        j->d_in.release();
+        j->d_how.release();
+        j->d_bytes.release();
+        j->d_scan_tmp.release();
+        j->d_u32.release();
+        j->d_tiles.release();
+        j->d_u64.release();
+        j->d_offs.release();
+        j->d_counters.release();
+    }
+    delete j;
+}
+
+const char *ngz_flow_json_last_error(ngz_flow_json *j) { return j ? j->last_error.c_str() : "null flow JSON stage"; }
+
+int ngz_flow_json_encode(ngz_flow_json *o, ngz_ctx *ctx, const ngz_batch_out *out, ngz_flow_json_stats *stats, void *hip_stream) {
+    if (!o || !ctx || !out) return NGZ_E_INVALID;
+    if (stats) memset(stats, 0, sizeof *stats);
+    o->have = false;
+    o->n_dgrams = o->n_bytes = 0;
+    o->launches = 0;
+    o->size_ms = o->offsets_ms = o->pack_ms = 0;
+    if (int rc = ngzs::check_ctx(o, ctx)) return rc;
+    const uint32_t S = out->n_slots, D = out->n_dgrams, NS = out->n_sets;
+    if (!ngzs::slot_table_ok(out) || S != ctx->slot_version.size() || D != ctx->last_in.n)
+        return ngzs::fail(o, NGZ_E_INVALID, "slot table: `out` is not the context's last decode");
+    if (NS && !out->sets) return ngzs::fail(o, NGZ_E_INVALID, "no set table");
+    if (!D) {  // no datagram: no kernel
+        o->have = true;
+        return NGZ_OK;
+    }
+
+    // the plan: every slot's record as items, as json_render_mode walks it (ngz_json.cpp)
+    std::vector<FSlot> slots(S);
+    std::vector<FItem> items;
+    std::vector<JName> names;
+    Pool pool;
+    uint64_t n_records = 0;
+    for (uint32_t s = 0; s < S; ++s) {
+        const ngz_slot_info &si = out->slots[s];
+        const int32_t vi = ctx->slot_version[s];
+        if (vi < 0 || (size_t)vi >= ctx->versions.size()) return ngzs::fail(o, NGZ_E_INVALID, "slot table: `out` is not the context's last decode");
+        const ngzh::Version &ver = ctx->versions[vi];
+        const uint32_t nf = (uint32_t)ver.specs.size();
+        if (nf > ver.fields.size()) return ngzs::fail(o, NGZ_E_INVALID, "a template without its column layout");
+        // every column starts at a multiple of 16 bytes: a cell is aligned to its width
+        if (si.n_records && (!si.columns || ((uintptr_t)si.columns & 15) || (si.capacity & 15) || si.capacity < si.n_records))
+            return ngzs::fail(o, NGZ_E_LIMIT, "unexpected column block alignment");
+        FSlot &fs = slots[s];
+        fs = FSlot{};
+        fs.item0 = (uint32_t)items.size();
+        fs.n_items = nf;
+        fs.n_rows = si.n_records;
+        n_records += si.n_records;
+        for (uint32_t f = 0; f < nf; ++f) {
+            const Spec &sp = ver.specs[f];
+            const DevField &fd = ver.plan.f[f];
+            FItem it{};
+            std::string pre, suf;
+            bool is_float = false;
+            if (!pick(sp, fd, pool, names, &it, &pre, &suf, &is_float))
+                return ngzs::fail(o, NGZ_E_LIMIT, "field " + ie_label(sp) + ": a column of a width the renderers cannot read");
+            if (is_float) fs.has_float = 1;
+            it.col = si.columns ? si.columns + (uint64_t)si.capacity * fd.col_off : nullptr;
+            it.pre = pool.add((f == ver.n_scope ? "],\"fields\":[" : f ? "," : "") + pre);
+            it.suf = pool.add(suf);
+            items.push_back(it);
+        }
+        fs.rec_head = pool.add("{\"scope_fields\":[");
+        fs.rec_tail = pool.add(ver.n_scope == nf ? "],\"fields\":[]}" : "]}");
+        fs.set_head = pool.add("{\"Data\":{\"id\":" + std::to_string(ver.tid) + ",\"records\":[");
+    }
+    if (names.size() > NGZ_FLOW_JSON_MAX_NAMES) return ngzs::fail(o, NGZ_E_LIMIT, "more sub-registry variants than NGZ_FLOW_JSON_MAX_NAMES");
+    FArgs A{};
+    A.fixed[T_V10_A] = pool.add("{\"IPFIX\":{\"version\":10,\"export_time\":");
+    A.fixed[T_SEQ] = pool.add(",\"sequence_number\":");
+    A.fixed[T_V10_DOMAIN] = pool.add(",\"observation_domain_id\":");
+    A.fixed[T_V9_A] = pool.add("{\"NetFlowV9\":{\"version\":9,\"sys_up_time\":");
+    A.fixed[T_V9_TIME] = pool.add(",\"unix_time\":");
+    A.fixed[T_V9_SOURCE] = pool.add(",\"source_id\":");
+    A.fixed[T_SETS] = pool.add(",\"sets\":[");
+    A.fixed[T_DGRAM_TAIL] = pool.add("]}}");
+    A.fixed[T_SET_TAIL] = pool.add("]}}");
+    A.fixed[T_UNASSIGNED] = pool.add("{\"Unassigned\":");
+    pool.b.resize(pool.b.size() + 4, 0);
+    std::vector<uint32_t> host_dgrams;  // (datagram, set position) order: ascending
+    for (const ngzh::TemplateSetJson &t : ctx->tmpl_sets)
+        if (host_dgrams.empty() || host_dgrams.back() != t.dgram) host_dgrams.push_back(t.dgram);
+    const uint64_t tile_cap = n_records / FJ_TILE + NS + 1;  // a set's last tile may be short
+    if (tile_cap >> 31 || pool.b.size() >> 31) return ngzs::fail(o, NGZ_E_LIMIT, "batch too large");
+
+    const uint64_t items_at = align256(slots.size() * sizeof(FSlot)), names_at = items_at + align256(items.size() * sizeof(FItem));
+    const uint64_t pool_at = names_at + align256(names.size() * sizeof(JName)), host_at = pool_at + align256(pool.b.size());
+    const uint64_t in_bytes = host_at + align256(host_dgrams.size() * sizeof(uint32_t)) + 256;
+    if (int rc = ngzs::device_init(o)) return rc;
+    NGZ_STAGE_HIP(o, hipSetDevice(o->device));
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+    size_t scan_a = 0, scan_b = 0;
+    if (hipcub::DeviceScan::ExclusiveSum(nullptr, scan_a, (const uint32_t *)nullptr, (uint32_t *)nullptr, (int)(NS + 1), st) != hipSuccess ||
+        hipcub::DeviceScan::ExclusiveSum(nullptr, scan_b, (const unsigned long long *)nullptr, (unsigned long long *)nullptr, (int)(D + 1), st) !=
+            hipSuccess)
+        return ngzs::fail(o, NGZ_E_DEVICE, "scan temp size");
+    const size_t scan_bytes = std::max(scan_a, scan_b);
+    const uint64_t n_u32 = 2ull * D + 2ull * (NS + 1) + tile_cap, n_u64 = tile_cap + 2ull * NS + D + 1;
+    if (o->h_in.reserve(in_bytes) || o->d_in.ensure(in_bytes) || o->d_how.ensure(D) || o->d_u32.ensure(n_u32) || o->d_tiles.ensure(tile_cap) ||
+        o->d_u64.ensure(n_u64) || o->d_offs.ensure(D + 1) || o->d_counters.ensure(C_COUNT) || o->d_scan_tmp.ensure(scan_bytes + 1) ||
+        o->h_back.reserve(C_COUNT + 2))
+        return ngzs::fail(o, NGZ_E_NOMEM, "flow JSON buffers");
+    uint8_t *h = o->h_in.p;
+    memset(h, 0, in_bytes);
+    if (S) memcpy(h, slots.data(), slots.size() * sizeof(FSlot));
+    if (!items.empty()) memcpy(h + items_at, items.data(), items.size() * sizeof(FItem));
+    if (!names.empty()) memcpy(h + names_at, names.data(), names.size() * sizeof(JName));
+    memcpy(h + pool_at, pool.b.data(), pool.b.size());
+    if (!host_dgrams.empty()) memcpy(h + host_at, host_dgrams.data(), host_dgrams.size() * sizeof(uint32_t));
+
+    A.slots = (const FSlot *)o->d_in.p;
+    A.items = (const FItem *)(o->d_in.p + items_at);
+    A.names = (const JName *)(o->d_in.p + names_at);
+    A.pool = (const uint32_t *)(o->d_in.p + pool_at);
+    A.host_dgrams = (const uint32_t *)(o->d_in.p + host_at);
+    A.n_host = (uint32_t)host_dgrams.size();
+    A.sets = out->sets;
+    A.hdr = out->dgrams;
+    A.in = ctx->last_in.bytes;
+    A.in_size = ctx->last_in.bytes_size;
+    A.n_sets = NS;
+    A.n_dgrams = D;
+    A.n_slots = S;
+    A.tile_cap = (uint32_t)tile_cap;
+    A.how = o->d_how.p;
+    A.dset0 = o->d_u32.p;
+    A.dset1 = A.dset0 + D;
+    A.ntiles = A.dset1 + D;
+    A.tile0 = A.ntiles + NS + 1;
+    A.tile_bytes = A.tile0 + NS + 1;
+    A.tiles = o->d_tiles.p;
+    A.tile_off = o->d_u64.p;
+    A.set_len = A.tile_off + tile_cap;
+    A.set_off = A.set_len + NS;
+    A.dlen = A.set_off + NS;
+    A.offs = o->d_offs.p;
+    A.counters = o->d_counters.p;
+
+    NGZ_STAGE_HIP(o, hipMemcpyAsync(o->d_in.p, h, in_bytes, hipMemcpyHostToDevice, st));
+    NGZ_STAGE_HIP(o, hipMemsetAsync(o->d_counters.p, 0, C_COUNT * sizeof(unsigned long long), st));
+    NGZ_STAGE_HIP(o, hipEventRecord(o->ev[0], st));
+    auto launch = [&](auto kernel, uint32_t nb, uint32_t threads, auto... args) {
+        hipLaunchKernelGGL(kernel, dim3(nb), dim3(threads), 0, st, args...);
+        ++o->launches;
+        return hipGetLastError();
+    };
+    NGZ_STAGE_HIP(o, launch(k_fj_dgrams, blocks(D), FJ_THREADS, A));
+    if (NS) {
+        NGZ_STAGE_HIP(o, launch(k_fj_sets, blocks(NS), FJ_THREADS, A));
+        NGZ_STAGE_HIP(o, launch(k_fj_tiles, blocks((uint64_t)NS + 1), FJ_THREADS, A));
+        NGZ_STAGE_HIP(o, hipcub::DeviceScan::ExclusiveSum(o->d_scan_tmp.p, scan_a, (const uint32_t *)A.ntiles, A.tile0, (int)(NS + 1), st));
+        ++o->launches;
+        NGZ_STAGE_HIP(o, launch(k_fj_fill, blocks(NS), FJ_THREADS, A));
+        const uint32_t nb = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((tile_cap + 3) / 4, (uint64_t)o->n_cus * 16));
+        NGZ_STAGE_HIP(o, launch(k_fj_size, nb, FJ_THREADS, A));
+    }
+    NGZ_STAGE_HIP(o, hipEventRecord(o->ev[1], st));
+    if (NS) NGZ_STAGE_HIP(o, launch(k_fj_set_len, blocks(NS), FJ_THREADS, A));
+    NGZ_STAGE_HIP(o, launch(k_fj_dgram_len, blocks(D), FJ_THREADS, A));
+    NGZ_STAGE_HIP(o, hipcub::DeviceScan::ExclusiveSum(o->d_scan_tmp.p, scan_b, (const unsigned long long *)A.dlen, A.offs, (int)(D + 1), st));
+    ++o->launches;
+    NGZ_STAGE_HIP(o, hipEventRecord(o->ev[2], st));
+    unsigned long long *hb = o->h_back.p;
+    hb[C_COUNT + 1] = 0;
+    NGZ_STAGE_HIP(o, hipMemcpyAsync(hb, o->d_counters.p, C_COUNT * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    NGZ_STAGE_HIP(o, hipMemcpyAsync(hb + C_COUNT, A.offs + D, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    if (NS) NGZ_STAGE_HIP(o, hipMemcpyAsync(hb + C_COUNT + 1, A.tile0 + NS, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    NGZ_STAGE_HIP(o, hipStreamSynchronize(st));
+    NGZ_STAGE_HIP(o, hipEventElapsedTime(&o->size_ms, o->ev[0], o->ev[1]));
+    NGZ_STAGE_HIP(o, hipEventElapsedTime(&o->offsets_ms, o->ev[1], o->ev[2]));
+    if (hb[C_ERR] & (ERR_SETS | ERR_TILES)) return ngzs::fail_sets(o);
+    if (hb[C_ERR] & ERR_VLEN) return ngzs::fail(o, NGZ_E_INVALID, "a variable-length cell outside the batch input");
+    const unsigned long long total = hb[C_COUNT];
+    const uint32_t n_tiles = (uint32_t)hb[C_COUNT + 1];
+    if (n_tiles > tile_cap) return ngzs::fail_sets(o);
+    if (o->d_bytes.ensure(total + NGZ_OUTPUT_GUARD + 16)) return ngzs::fail(o, NGZ_E_NOMEM, "flow JSON bytes");
+    A.out = o->d_bytes.p;
+    A.total = total;
+    NGZ_STAGE_HIP(o, hipMemsetAsync(A.out + total, 0xA5, NGZ_OUTPUT_GUARD, st));
+    if (total) {
+        NGZ_STAGE_HIP(o, hipEventRecord(o->ev[0], st));
+        NGZ_STAGE_HIP(o, launch(k_fj_glue_dgrams, blocks(D), FJ_THREADS, A));
+        if (NS) NGZ_STAGE_HIP(o, launch(k_fj_glue_sets, blocks(NS), FJ_THREADS, A));
+        if (n_tiles) {
+            const uint32_t nb = (uint32_t)std::min<uint64_t>(n_tiles, (uint64_t)o->n_cus * 16);
+            NGZ_STAGE_HIP(o, launch(k_fj_pack<JAcc>, nb, 64u, A, n_tiles));
+        }
+        NGZ_STAGE_HIP(o, hipEventRecord(o->ev[3], st));
+    }
+    NGZ_STAGE_HIP(o, hipMemcpyAsync(hb + C_COUNT, o->d_counters.p, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    NGZ_STAGE_HIP(o, hipStreamSynchronize(st));
+    if (total) NGZ_STAGE_HIP(o, hipEventElapsedTime(&o->pack_ms, o->ev[0], o->ev[3]));
+    if (hb[C_COUNT] & ERR_VLEN) return ngzs::fail(o, NGZ_E_INVALID, "a variable-length cell outside the batch input");
+    o->have = true;
+    o->n_dgrams = D;
+    o->n_bytes = total;
+    if (stats) *stats = ngz_flow_json_stats{hb[C_LINES], total, hb[C_TEMPLATE], hb[C_FLOAT], hb[C_NOT_OK]};
+    return NGZ_OK;
+}
+
+int ngz_flow_json_result(ngz_flow_json *o, const uint8_t **bytes, const uint64_t **offsets, const uint8_t **how, uint64_t *n_dgrams,
+                         uint64_t *n_bytes) {
+    if (!o) return NGZ_E_INVALID;
+    if (!o->have) return ngzs::fail(o, NGZ_E_INVALID, "no encode to read");
+    if (bytes) *bytes = o->n_dgrams ? o->d_bytes.p : nullptr;
+    if (offsets) *offsets = o->n_dgrams ? (const uint64_t *)o->d_offs.p : nullptr;
+    if (how) *how = o->n_dgrams ? o->d_how.p : nullptr;
+    if (n_dgrams) *n_dgrams = o->n_dgrams;
+    if (n_bytes) *n_bytes = o->n_bytes;
+    return NGZ_OK;
+}
+
+int ngz_flow_json_to_host(ngz_flow_json *o, uint8_t *bytes, uint64_t bytes_cap, uint64_t *offsets, uint64_t offsets_cap, uint8_t *how,
+                          uint64_t how_cap) {
+    if (!o) return NGZ_E_INVALID;
+    if (!o->have) return ngzs::fail(o, NGZ_E_INVALID, "no encode to read");
+    if ((bytes && bytes_cap < o->n_bytes) || (offsets && offsets_cap < o->n_dgrams + 1) || (how && how_cap < o->n_dgrams))
+        return ngzs::fail(o, NGZ_E_INVALID, "a buffer smaller than the result");
+    if (!o->n_dgrams) {
+        if (offsets && offsets_cap) offsets[0] = 0;
+        return NGZ_OK;
+    }
+    NGZ_STAGE_HIP(o, hipSetDevice(o->device));
+    if (bytes) {
+        const uint64_t n = bytes_cap >= o->n_bytes + NGZ_OUTPUT_GUARD ? o->n_bytes + NGZ_OUTPUT_GUARD : o->n_bytes;
+        if (n) NGZ_STAGE_HIP(o, hipMemcpy(bytes, o->d_bytes.p, n, hipMemcpyDeviceToHost));
+    }
+    if (offsets) NGZ_STAGE_HIP(o, hipMemcpy(offsets, o->d_offs.p, (o->n_dgrams + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (how) NGZ_STAGE_HIP(o, hipMemcpy(how, o->d_how.p, o->n_dgrams, hipMemcpyDeviceToHost));
+    return NGZ_OK;
+}
+
+int ngz_flow_json_last_timing(ngz_flow_json *o, float *size_ms, float *offsets_ms, float *pack_ms) {
+    if (!o || !size_ms || !offsets_ms || !pack_ms) return NGZ_E_INVALID;
+    *size_ms = o->size_ms;
+    *offsets_ms = o->offsets_ms;
+    *pack_ms = o->pack_ms;
+    return NGZ_OK;
+}
+
+int ngz_flow_json_last_launches(ngz_flow_json *o) { return o ? o->launches : NGZ_E_INVALID; }
+
+}  // extern "C"

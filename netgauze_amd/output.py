@@ -13,6 +13,10 @@ the reference's Avro publisher sends.  `encode(aggregator, raw)` takes the rows 
 `AggFlowJson()` is the JSON publisher over the same rows (include/ngz/flow_agg_json.h): `encode(aggregator,
 raw, shard_id, seq0, export_time_ms)` renders on the device the lines `FlowAggregator.flowinfo_json` gives.
 
+`FlowJson()` is the JSON publisher over the decoded messages themselves (include/ngz/flow_json.h):
+`encode(batch)` renders on the device the line `DecodedBatch.json(d)` gives for every datagram it does not
+leave to the host (`how`); `lines(batch)` fills those in.
+
 A field is a dict: {"name", "select": "Single" | "Coalesce" | "Multi" | "Layer2SegmentId", "refs":
 [(pen, ie_id, index)], "transform": "Identity" | "String" | "MplsIndex" | ..., "default": None |
 (RawValue kind, value) such as ("U32", 7) or ("String", "n/a"), "encap": the Layer2SegmentId's
@@ -308,3 +312,83 @@ class AggFlowJson:
     @property
     def last_launches(self):
         return int(lib().ngz_agg_json_last_launches(self._h))
+
+
+class FlowJson:
+    """The serde JSON lines of the decoded messages of a batch, rendered on the device (ngz_flow_json): for
+    every datagram whose `how` is LINE, what `DecodedBatch.json(d)` returns."""
+
+    NONE, LINE, HOST = _lib.NGZ_FLOW_JSON_NONE, _lib.NGZ_FLOW_JSON_LINE, _lib.NGZ_FLOW_JSON_HOST
+
+    def __init__(self, device=0):
+        h = ctypes.c_void_p()
+        rc = lib().ngz_flow_json_create(device, ctypes.byref(h))
+        if rc != 0:
+            raise OutputError("ngz_flow_json_create failed (%d)" % rc, rc)
+        self._h = h
+        self.device = device
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            lib().ngz_flow_json_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        if sys.is_finalizing():  # the HIP runtime may be torn down already: leave it to the process exit
+            return
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, rc):
+        if rc < 0:
+            raise OutputError("%s (%d)" % (lib().ngz_flow_json_last_error(self._h).decode(), rc), rc)
+        return rc
+
+    def encode(self, batch, stream=None):
+        """Render the codec's latest DecodedBatch; this encode's counters.  The batch's input must still be
+        valid: variable-length values are read from it."""
+        if batch.generation != batch._codec.generation:
+            raise OutputError("stale DecodedBatch: its codec has decoded another batch since", _lib.NGZ_E_INVALID)
+        st = _lib.FlowJsonStats()
+        self._check(lib().ngz_flow_json_encode(self._h, batch._codec._ctx, ctypes.byref(batch.out), ctypes.byref(st),
+                                               ctypes.c_void_p(stream) if stream else None))
+        return st.as_dict()
+
+    def result_pointers(self):
+        """(device pointers of the lines, of the u64 offsets and of `how`, datagrams, bytes) of the last encode."""
+        b, o, w, n, nb = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_uint64(), ctypes.c_uint64()
+        self._check(lib().ngz_flow_json_result(self._h, ctypes.byref(b), ctypes.byref(o), ctypes.byref(w), ctypes.byref(n), ctypes.byref(nb)))
+        return b.value, o.value, w.value, int(n.value), int(nb.value)
+
+    def result(self, guard=False):
+        """The last encode on the host: (lines back to back as bytes, offsets as a uint64 array of datagrams + 1,
+        `how` as a uint8 array); with `guard` the guard bytes the stage keeps after the lines follow them."""
+        _b, _o, _w, n, nb = self.result_pointers()
+        data = np.empty(nb + (_lib.NGZ_OUTPUT_GUARD if guard else 0), dtype=np.uint8)
+        offs = np.zeros(n + 1, dtype=np.uint64)
+        how = np.zeros(n, dtype=np.uint8)
+        self._check(lib().ngz_flow_json_to_host(self._h, data.ctypes.data, data.size, offs.ctypes.data, offs.size, how.ctypes.data, how.size))
+        return data.tobytes(), offs, how
+
+    def lines(self, batch):
+        """Encode `batch` and return [(datagram, text)] of its OK datagrams: the device's lines, and
+        `batch.json(d)` for the datagrams it leaves to the host."""
+        self.encode(batch)
+        data, offs, how = self.result()
+        offs = offs.tolist()
+        return [(d, data[offs[d]:offs[d + 1]].decode("utf-8") if h == self.LINE else batch.json(d))
+                for d, h in enumerate(how.tolist()) if h != self.NONE]
+
+    def last_ms(self):
+        """(size pass, offsets, glue and pack passes) of the last encode, device milliseconds."""
+        t = [ctypes.c_float() for _ in range(3)]
+        lib().ngz_flow_json_last_timing(self._h, *[ctypes.byref(x) for x in t])
+        return tuple(x.value for x in t)
+
+    last_timing = last_ms
+
+    @property
+    def last_launches(self):
+        return int(lib().ngz_flow_json_last_launches(self._h))
