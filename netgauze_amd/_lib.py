@@ -134,6 +134,14 @@ FLOW_JSON_FUNCTIONS = [
 ]
 NGZ_FLOW_JSON_ABI_VERSION = 1
 NGZ_FLOW_JSON_NONE, NGZ_FLOW_JSON_LINE, NGZ_FLOW_JSON_HOST = 0, 1, 2
+# include/ngz/flow_wire.h
+WIRE_FUNCTIONS = [
+    "ngz_wire_abi_version", "ngz_dgram_wire", "ngz_dgram_wire_aligned", "ngz_wire_create", "ngz_wire_destroy", "ngz_wire_last_error",
+    "ngz_wire_set_option", "ngz_wire_encode", "ngz_wire_result", "ngz_wire_to_host", "ngz_wire_last_timing", "ngz_wire_last_launches",
+]
+NGZ_WIRE_ABI_VERSION = 1
+NGZ_WIRE_NONE, NGZ_WIRE_WIRE, NGZ_WIRE_HOST, NGZ_WIRE_UNWRITABLE = 0, 1, 2, 3
+NGZ_WIRE_OPT_ALIGN4 = 1
 NGZ_ENRICH_MAX_SCOPE_FIELDS, NGZ_ENRICH_MAX_SHAPES, NGZ_ENRICH_MAX_COLUMNS = 4, 8, 32
 NGZ_ENRICH_MAX_KEY_BYTES, NGZ_ENRICH_MAX_DOMAINS = 16, 253
 NGZ_RENORM_OPTIONS = 0x100
@@ -425,6 +433,15 @@ class FlowJsonStats(ctypes.Structure):
     """ngz_flow_json_stats."""
     _fields_ = [("lines", ctypes.c_uint64), ("bytes", ctypes.c_uint64), ("left_template", ctypes.c_uint64),
                 ("left_float", ctypes.c_uint64), ("not_ok", ctypes.c_uint64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class WireStats(ctypes.Structure):
+    """ngz_wire_stats."""
+    _fields_ = [("wire", ctypes.c_uint64), ("bytes", ctypes.c_uint64), ("left_template", ctypes.c_uint64),
+                ("unwritable", ctypes.c_uint64), ("not_ok", ctypes.c_uint64)]
 
     def as_dict(self):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
@@ -772,6 +789,31 @@ def load():
     lib.ngz_flow_json_last_timing.restype = I
     lib.ngz_flow_json_last_launches.argtypes = [P]
     lib.ngz_flow_json_last_launches.restype = I
+    # IPFIX / NetFlow v9 messages of decoded datagrams (flow_wire.h)
+    lib.ngz_wire_abi_version.argtypes, lib.ngz_wire_abi_version.restype = [], I
+    if lib.ngz_wire_abi_version() != NGZ_WIRE_ABI_VERSION:
+        raise RuntimeError("netgauze_amd: %s has wire ABI version %d, this binding needs %d -- rebuild it"
+                           % (LIB_PATH, lib.ngz_wire_abi_version(), NGZ_WIRE_ABI_VERSION))
+    for fn in (lib.ngz_dgram_wire, lib.ngz_dgram_wire_aligned):
+        fn.argtypes, fn.restype = [P, U32, P, ctypes.c_size_t], ctypes.c_int64
+    lib.ngz_wire_create.argtypes = [I, ctypes.POINTER(P)]
+    lib.ngz_wire_create.restype = I
+    lib.ngz_wire_destroy.argtypes = [P]
+    lib.ngz_wire_destroy.restype = None
+    lib.ngz_wire_last_error.argtypes = [P]
+    lib.ngz_wire_last_error.restype = ctypes.c_char_p
+    lib.ngz_wire_set_option.argtypes = [P, I, ctypes.c_int64]
+    lib.ngz_wire_set_option.restype = I
+    lib.ngz_wire_encode.argtypes = [P, P, ctypes.POINTER(BatchOut), ctypes.POINTER(WireStats), P]
+    lib.ngz_wire_encode.restype = I
+    lib.ngz_wire_result.argtypes = [P, ctypes.POINTER(P), ctypes.POINTER(P), ctypes.POINTER(P), ctypes.POINTER(U64), ctypes.POINTER(U64)]
+    lib.ngz_wire_result.restype = I
+    lib.ngz_wire_to_host.argtypes = [P, P, U64, P, U64, P, U64]
+    lib.ngz_wire_to_host.restype = I
+    lib.ngz_wire_last_timing.argtypes = [P] + [ctypes.POINTER(ctypes.c_float)] * 4
+    lib.ngz_wire_last_timing.restype = I
+    lib.ngz_wire_last_launches.argtypes = [P]
+    lib.ngz_wire_last_launches.restype = I
     # ingest (flow_ingest.h)
     lib.ngz_pcap_open.argtypes = [ctypes.c_char_p, ctypes.POINTER(P)]
     lib.ngz_pcap_open.restype = I

@@ -145,6 +145,18 @@ class DecodedBatch:
         lib().ngz_dgram_json(self._codec._ctx, d, buf, n + 1)
         return buf.raw[:n].decode("utf-8")
 
+    def dgram_wire(self, d, align4=False):
+        """The IPFIX / NetFlow v9 message the reference's writer gives for datagram d's packet, written
+        from the decoded columns (ngz_dgram_wire; align4: the NFv9 align_to_4_bytes option); None when
+        the datagram is not OK or holds a data set of an unwritable template (flow_wire.h)."""
+        fn = lib().ngz_dgram_wire_aligned if align4 else lib().ngz_dgram_wire
+        n = fn(self._codec._ctx, d, None, 0)
+        if n < 0:
+            return None
+        buf = ctypes.create_string_buffer(max(n, 1))
+        fn(self._codec._ctx, d, buf, n)
+        return buf.raw[:n]
+
     def record_fields(self, d, s, r):
         """ngz_record_fields: the fields of record r of datagram d's data set s (scope first) as
         [(pen, ie_id, kind, dtype, flags, wire_length, wire_offset, value bytes)] -- the reference's
