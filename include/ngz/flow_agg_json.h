@@ -25,10 +25,13 @@
  * fraction digits, nanos >= 10^9 as second 60, years outside 0..9999 signed), TCPHeaderFlags,
  * sub-registry enums flat and nested, and the four tag shapes (IANA, vendor, vendor-unknown, Unknown).
  *
- * Floats are refused.  A key or aggregated field whose IE is float32 or float64 makes the encode fail
- * with NGZ_OUTPUT_E_UNSUPPORTED and a message naming the IE, before any launch: serde_json's text for
- * them is ryu's shortest round trip, which needs its own tables and proof.  Nothing is approximated;
- * ngz_agg_flowinfo_json remains the way for such layouts.
+ * Floats: serde_json's text for them is ryu's shortest round trip.  By default a key or aggregated field
+ * whose IE is float32 or float64 makes the encode fail with NGZ_OUTPUT_E_UNSUPPORTED and a message naming
+ * the IE, before any launch, and ngz_agg_flowinfo_json remains the way for such layouts.  With
+ * NGZ_AGG_JSON_OPT_FLOATS 1 a float64 key or aggregated value (the aggregator's f64 value class: sums in
+ * record order, Min / Max in its float order) is rendered on the device, null for NaN and the infinities;
+ * float32 is still refused: no IE of the registry has that type, and its text would need the 32-bit variant
+ * of the routine.  Nothing is approximated.
  *
  * Rows: as flow_agg_output.h.  `rows` is what the LAST ngz_agg_flush / ngz_agg_emit of `agg` copied to
  * the host.  Rows that carry different take_ids, or whose take_id is not the aggregator's last as far as
@@ -67,6 +70,11 @@ extern "C" {
  * never what it writes.  NGZ_AGG_JSON_OPT_WRITER 0 (default): the accumulating dword writer; 1: the plain
  * byte writer of the Avro stages.  Default as measured, profiles/agg_json/summary.txt. */
 #define NGZ_AGG_JSON_OPT_WRITER 1
+/* Unlike NGZ_AGG_JSON_OPT_WRITER this option changes what an encode accepts, never a byte of a line it
+ * accepted before.  NGZ_AGG_JSON_OPT_FLOATS 0 (default): a float key or aggregated field is refused as
+ * above.  1: a float64 one is rendered; float32 is still refused.  A layout without floats launches the same
+ * kernels under both values. */
+#define NGZ_AGG_JSON_OPT_FLOATS 2
 
 typedef struct ngz_agg_json ngz_agg_json;
 

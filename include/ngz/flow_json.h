@@ -15,10 +15,17 @@
  *   NGZ_FLOW_JSON_HOST  an OK datagram the device leaves to ngz_dgram_json: it carries a template or
  *                       options-template set (their texts live on the host with the template state; the
  *                       host uploads the indices of such datagrams, which are rare), or a data set of a
- *                       template with a float32 / float64 field (serde_json's text for them is ryu's
- *                       shortest round trip, which stays out as in flow_agg_json.h; here it costs those
- *                       datagrams only, never the batch).
+ *                       template with a float field the device does not render: a float64 field while
+ *                       NGZ_FLOW_JSON_OPT_FLOATS is 0, the default, and a float32 field always.  It costs
+ *                       those datagrams only, never the batch.
  * Nothing is refused and nothing approximated.
+ *
+ * Floats: serde_json's text of a float is ryu's shortest round trip.  With NGZ_FLOW_JSON_OPT_FLOATS 1 a
+ * float64 field (samplingProbability, absoluteError, relativeError, the confidence-interval bounds and
+ * confidenceLevel: every float IE of the registry) is rendered on the device like any other field, null for
+ * NaN and the infinities, and its datagrams are NGZ_FLOW_JSON_LINE.  float32 stays with the host: no IE of
+ * the registry has that type, so no template can reach it, and its text would need the 32-bit variant of the
+ * routine.  Template-set datagrams stay with the host under either value.
  *
  * Scope: the plain decoded FlowInfo only.  The renormalized and the enriched renderer modes
  * (ngz_renorm_batch_json, ngz_enrich_batch_json) and the line callback's `consumed` are not rendered here.
@@ -26,7 +33,7 @@
  * A line: the IPFIX head (export_time as RFC 3339 text, sequence number, observation domain) or the
  * NetFlow v9 head (sys_up_time, unix_time, sequence number, source_id), then the data sets in stream
  * order, each with its template id and its records, each record its scope fields and fields in template
- * order.  Rendered: everything ngz_dgram_json renders but floats: unsigned and signed integers, booleans,
+ * order.  Rendered: everything ngz_dgram_json renders (floats as above): unsigned and signed integers, booleans,
  * IPv4 and Ipv6Addr Display text, byte lists (macAddress, fixed bytes, unsigned256, octetArray, list-typed
  * and unknown IEs), strings with serde_json's escapes (fixed ones cut at the first NUL), the dateTime
  * storages as chrono's RFC 3339 text, TCPHeaderFlags, sub-registry enums flat and nested, the four tag
@@ -83,6 +90,19 @@ int ngz_flow_json_abi_version(void);
 int ngz_flow_json_create(int device, ngz_flow_json **out);
 void ngz_flow_json_destroy(ngz_flow_json *j);
 const char *ngz_flow_json_last_error(ngz_flow_json *j);
+
+/* NGZ_FLOW_JSON_OPT_FLOATS 0 (default): a data set of a template with a float64 field leaves its datagram
+ * to the host (NGZ_FLOW_JSON_HOST, counted in left_float).  1: such a template is planned like any other and
+ * its datagrams are rendered; left_float then counts float32 templates only.  The option changes which
+ * datagrams are rendered, never a rendered byte; a batch without float fields launches the same kernels
+ * under both values.  NGZ_E_INVALID: an unknown option or value. */
+#define NGZ_FLOW_JSON_OPT_FLOATS 1
+int ngz_flow_json_set_option(ngz_flow_json *j, int opt, int64_t value);
+
+/* serde_json's text of the float64 with bit pattern `bits`, through the routine the device kernels run,
+ * compiled for the host: so that it can be checked where there is no device.  Makes no HIP call.  Returns
+ * the length (at most 24; no terminator is written), or NGZ_E_INVALID when buf is NULL or cap is smaller. */
+int ngz_flow_json_f64_text(uint64_t bits, char *buf, size_t cap);
 
 /* The stage over the batch last decoded on ctx (`out` is that decode's result).  Synchronous.  Reads the
  * decoded columns, the set table, the datagram headers and the batch input; writes nothing into the

@@ -127,12 +127,15 @@ AGG_JSON_FUNCTIONS = [
 ]
 NGZ_AGG_JSON_ABI_VERSION = 1
 NGZ_AGG_JSON_OPT_WRITER = 1
+NGZ_AGG_JSON_OPT_FLOATS = 2
 # include/ngz/flow_json.h
 FLOW_JSON_FUNCTIONS = [
     "ngz_flow_json_abi_version", "ngz_flow_json_create", "ngz_flow_json_destroy", "ngz_flow_json_last_error", "ngz_flow_json_encode",
     "ngz_flow_json_result", "ngz_flow_json_to_host", "ngz_flow_json_last_timing", "ngz_flow_json_last_launches",
+    "ngz_flow_json_set_option", "ngz_flow_json_f64_text",
 ]
 NGZ_FLOW_JSON_ABI_VERSION = 1
+NGZ_FLOW_JSON_OPT_FLOATS = 1
 NGZ_FLOW_JSON_NONE, NGZ_FLOW_JSON_LINE, NGZ_FLOW_JSON_HOST = 0, 1, 2
 # include/ngz/flow_wire.h
 WIRE_FUNCTIONS = [
@@ -789,6 +792,10 @@ def load():
     lib.ngz_flow_json_last_timing.restype = I
     lib.ngz_flow_json_last_launches.argtypes = [P]
     lib.ngz_flow_json_last_launches.restype = I
+    lib.ngz_flow_json_set_option.argtypes = [P, I, ctypes.c_int64]
+    lib.ngz_flow_json_set_option.restype = I
+    lib.ngz_flow_json_f64_text.argtypes = [U64, ctypes.c_char_p, ctypes.c_size_t]
+    lib.ngz_flow_json_f64_text.restype = I
     # IPFIX / NetFlow v9 messages of decoded datagrams (flow_wire.h)
     lib.ngz_wire_abi_version.argtypes, lib.ngz_wire_abi_version.restype = [], I
     if lib.ngz_wire_abi_version() != NGZ_WIRE_ABI_VERSION:

@@ -14,7 +14,9 @@
 //                    range and goes out in 16-byte stores (pack_tile, ngz_output_enc.h); a line longer
 //                    than the image goes straight out through the byte writer.
 // One set of renderers, templated on the writer, serves both passes: the sizes are the packed bytes by
-// construction.
+// construction.  Both kernels have a second instantiation (FLT) whose renderer knows float64 (put_f64,
+// ngz_f64_dev.h), launched in their place when the plan has a float item (NGZ_AGG_JSON_OPT_FLOATS): a layout
+// without floats runs the kernels it ran before.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
@@ -26,6 +28,7 @@
 #include "ngz/flow_agg_json.h"
 #include "ngz_agg_rows.h"
 #include "ngz_host.h"
+#include "ngz_f64_dev.h"
 #include "ngz_json_dev.h"
 #include "ngz_output_enc.h"
 #include "ngz_stage.h"
@@ -48,7 +51,7 @@ enum : uint8_t { P_KEY, P_VAL, P_ALWAYS, P_PEER4, P_PEER6, P_PORTS, P_DOMAINS, P
 enum : uint8_t { L_INT, L_PTR, L_STRZ, L_BVAL, L_WSTART, L_WEND, L_PEER4, L_PEER6, L_MEMBER };  // how its value is read
 enum : uint8_t {  // put_value of ngz_json.cpp, case by case
     RD_NULL, RD_U64, RD_I64, RD_BOOL, RD_IP4, RD_IP6, RD_LIST, RD_STR, RD_DT_SECS, RD_DT_MS, RD_DT_FRAC_KEY, RD_DT_FRAC_VAL,
-    RD_TCP, RD_SUBREG, RD_SUBREG_NESTED
+    RD_TCP, RD_SUBREG, RD_SUBREG_NESTED, RD_F64
 };
 enum { T_V10_A, T_V10_B, T_V9_A, T_V9_B, T_V9_C, T_TAIL, T_UNASSIGNED, T_COUNT };
 
@@ -136,8 +139,14 @@ __device__ __forceinline__ void load_value(const JPlan &P, const JArgs &A, const
     }
 }
 
-template <class W>
+template <bool FLT, class W>
 __device__ __forceinline__ void render_value(W &w, const JPlan &P, const JArgs &A, const JItem &it, const JCell &c) {
+    if constexpr (FLT) {  // outside the switch: without FLT this function is what it was
+        if (it.rend == RD_F64) {  // the aggregator's f64 value class and a float64 key cell: the bits, L_INT at 8 bytes
+            put_f64(w, c.v);
+            return;
+        }
+    }
     switch (it.rend) {
     case RD_U64: put_dec(w, c.v); break;
     case RD_I64: {
@@ -178,7 +187,7 @@ __device__ __forceinline__ uint32_t peer_family(const JArgs &A, const uint8_t *R
 }
 
 // Row g's line: the head by the flow type, the present items, the closing text
-template <class W>
+template <bool FLT, class W>
 __device__ __forceinline__ void render_row(const JPlan &P, const JArgs &A, const uint8_t *R, uint32_t g, W &w, uint32_t *err) {
     auto fixed = [&](int t) { w.text(A.pool + P.fixed[t].off / 4u, P.fixed[t].len); };
     if (R[R_FLOW_TYPE] == 10) {
@@ -199,7 +208,7 @@ __device__ __forceinline__ void render_row(const JPlan &P, const JArgs &A, const
         if (!first) w.push(',', 1);
         first = false;
         w.text(A.pool + it.pre.off / 4u, it.pre.len);
-        render_value(w, P, A, it, c);
+        render_value<FLT>(w, P, A, it, c);
         w.text(A.pool + it.suf.off / 4u, it.suf.len);
     };
     for (uint32_t i = 0; i < P.n_items; ++i) {
@@ -228,7 +237,7 @@ __device__ __forceinline__ void render_row(const JPlan &P, const JArgs &A, const
 // ---------------------------------------------------------------------------------------------
 // kernels
 // ---------------------------------------------------------------------------------------------
-template <uint32_t STAGE>
+template <uint32_t STAGE, bool FLT>
 __global__ __launch_bounds__(JS_THREADS) void k_agg_json_size(const JArgs A) {
     __shared__ __attribute__((aligned(16))) uint8_t stage[STAGE];
     const uint32_t lane = threadIdx.x, T = A.tile;
@@ -240,7 +249,7 @@ __global__ __launch_bounds__(JS_THREADS) void k_agg_json_size(const JArgs A) {
         const uint32_t row0 = tile * T, nt = min(T, A.n_rows - row0);
         stage_rows(A.rows, A.row_bytes, row0, nt, stage, lane);
         JCount w;
-        if (lane < nt) render_row(P, A, stage + lane * (A.row_bytes + AO_PAD), row0 + lane, w, &err);
+        if (lane < nt) render_row<FLT>(P, A, stage + lane * (A.row_bytes + AO_PAD), row0 + lane, w, &err);
         // four lengths per 16-byte store: T and row0 are multiples of four, rows past n_rows count 0
         const uint32_t n1 = __shfl_down(w.n, 1, 64), n2 = __shfl_down(w.n, 2, 64), n3 = __shfl_down(w.n, 3, 64);
         if (!(lane & 3u) && lane < nt) *(uint4 *)(A.lens + row0 + lane) = make_uint4(w.n, n1, n2, n3);
@@ -250,7 +259,7 @@ __global__ __launch_bounds__(JS_THREADS) void k_agg_json_size(const JArgs A) {
     if (err) atomicOr(A.err, err);
 }
 
-template <uint32_t STAGE, class WImg>
+template <uint32_t STAGE, class WImg, bool FLT>
 __global__ __launch_bounds__(JS_THREADS) void k_agg_json_pack(const JArgs A) {
     __shared__ __attribute__((aligned(16))) uint8_t stage[STAGE];
     __shared__ __attribute__((aligned(16))) uint8_t img[JS_IMG + 16];  // pack_tile's
@@ -266,7 +275,7 @@ __global__ __launch_bounds__(JS_THREADS) void k_agg_json_pack(const JArgs A) {
         const unsigned long long base = __shfl(a, 0, 64);
         const uint32_t rel0 = (uint32_t)(a - base), rel1 = (uint32_t)(b - base);
         ngzenc::pack_tile<JS_IMG, WImg, JByte>(lane, nt, base, rel0, rel1, A.out, A.total, img,
-                                               [&](auto &w) { render_row(P, A, R, row0 + lane, w, &err); });
+                                               [&](auto &w) { render_row<FLT>(P, A, R, row0 + lane, w, &err); });
         __threadfence_block();
         __builtin_amdgcn_wave_barrier();  // the stage is rewritten by the next tile
     }
@@ -278,11 +287,23 @@ struct ToU64 {
 };
 using LenIter = hipcub::TransformInputIterator<unsigned long long, ToU64, const uint32_t *>;
 
+// The two kernels of a row size, a writer and a renderer set
+template <bool FLT>
+void (*size_kernel(bool small))(const JArgs) {
+    return small ? k_agg_json_size<JS_STAGE_SMALL, FLT> : k_agg_json_size<JS_STAGE_LARGE, FLT>;
+}
+template <bool FLT>
+void (*pack_kernel(bool small, bool bytes))(const JArgs) {
+    return bytes ? (small ? k_agg_json_pack<JS_STAGE_SMALL, JByte, FLT> : k_agg_json_pack<JS_STAGE_LARGE, JByte, FLT>)
+                 : (small ? k_agg_json_pack<JS_STAGE_SMALL, JAcc, FLT> : k_agg_json_pack<JS_STAGE_LARGE, JAcc, FLT>);
+}
+
 }  // namespace
 
 struct ngz_agg_json : ngzs::Stage {
     ngz_agg_json() : Stage(4) {}
-    int writer = 0;  // NGZ_AGG_JSON_OPT_WRITER
+    int writer = 0;       // NGZ_AGG_JSON_OPT_WRITER
+    bool floats = false;  // NGZ_AGG_JSON_OPT_FLOATS
     float upload_ms = 0, size_ms = 0, pack_ms = 0;
     int launches = 0;
     uint64_t n_rows = 0, n_bytes = 0;  // the last encode
@@ -409,8 +430,10 @@ const char *ngz_agg_json_last_error(ngz_agg_json *j) { return j ? j->last_error.
 
 int ngz_agg_json_set_option(ngz_agg_json *j, int opt, int64_t value) {
     if (!j) return NGZ_E_INVALID;
-    if (opt != NGZ_AGG_JSON_OPT_WRITER || (value != 0 && value != 1)) return ngzs::fail(j, NGZ_E_INVALID, "unknown option or value");
-    j->writer = (int)value;
+    if ((opt != NGZ_AGG_JSON_OPT_WRITER && opt != NGZ_AGG_JSON_OPT_FLOATS) || (value != 0 && value != 1))
+        return ngzs::fail(j, NGZ_E_INVALID, "unknown option or value");
+    if (opt == NGZ_AGG_JSON_OPT_WRITER) j->writer = (int)value;
+    else j->floats = value != 0;
     return NGZ_OK;
 }
 
@@ -443,12 +466,15 @@ int ngz_agg_json_encode(ngz_agg_json *o, ngz_agg *agg, const void *rows, uint64_
     Pool pool;
     std::vector<JName> names;
     uint32_t ni = 0;
+    bool use_float = false;  // the plan has a float item: the kernels' float instantiation
     auto item = [&](uint32_t pen, uint16_t ie, uint8_t pres, uint32_t bit, uint32_t off, uint8_t kind, uint16_t width, int bval,
                     int load) -> int {
         if (ni == JS_MAX_ITEMS) return ngzs::fail(o, NGZ_E_LIMIT, "more than 64 fields in a group's record");
         const Spec s = spec_of(pen, ie);
         const bool known = s.kind == ngzh::IK_IANA || s.kind == ngzh::IK_VENDOR;
-        if ((pres == P_KEY || pres == P_VAL) && known && (s.dtype == ngzh::DT_float32 || s.dtype == ngzh::DT_float64))
+        const bool is_float = (pres == P_KEY || pres == P_VAL) && known && (s.dtype == ngzh::DT_float32 || s.dtype == ngzh::DT_float64);
+        const bool f64 = is_float && o->floats && s.dtype == ngzh::DT_float64;
+        if (is_float && !f64)
             return ngzs::fail(o, NGZ_OUTPUT_E_UNSUPPORTED,
                               "field " + ie_label(s) + ": float text is not rendered on the device (ngz_agg_flowinfo_json renders it)");
         JItem it{};
@@ -462,6 +488,12 @@ int ngz_agg_json_encode(ngz_agg_json *o, ngz_agg *agg, const void *rows, uint64_
             return ngzs::fail(o, NGZ_E_LIMIT, "field " + ie_label(s) + ": an integer storage that is not 1, 2, 4 or 8 bytes wide");
         }
         if (load >= 0) it.load = (uint8_t)load;
+        if (f64) {  // the bits as the row stores them: the f64 value class, or a key's 8-byte column cell
+            if (it.load != L_INT || it.width != 8)
+                return ngzs::fail(o, NGZ_E_LIMIT, "field " + ie_label(s) + ": a float64 storage that is not 8 bytes wide");
+            it.rend = RD_F64;
+            use_float = true;
+        }
         tag_text(s, pool, &it);
         P.items[ni++] = it;
         return NGZ_OK;
@@ -632,7 +664,7 @@ int ngz_agg_json_encode(ngz_agg_json *o, ngz_agg *agg, const void *rows, uint64_
     const uint64_t tiles = (n_rows + tile - 1) / tile;
     const uint32_t nb = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(tiles, (uint64_t)o->n_cus * 16));
     const bool small = rb == 128;
-    hipLaunchKernelGGL(small ? k_agg_json_size<JS_STAGE_SMALL> : k_agg_json_size<JS_STAGE_LARGE>, dim3(nb), dim3(JS_THREADS), 0, st, A);
+    hipLaunchKernelGGL(use_float ? size_kernel<true>(small) : size_kernel<false>(small), dim3(nb), dim3(JS_THREADS), 0, st, A);
     NGZ_STAGE_HIP(o, hipGetLastError());
     NGZ_STAGE_HIP(o, hipcub::DeviceScan::ExclusiveSum(o->d_scan_tmp.p, scan_bytes, LenIter(A.lens, ToU64()), o->d_offs.p, (int)(n_rows + 1), st));
     o->launches += 2;
@@ -650,9 +682,8 @@ int ngz_agg_json_encode(ngz_agg_json *o, ngz_agg *agg, const void *rows, uint64_
     NGZ_STAGE_HIP(o, hipMemsetAsync(A.out + total, 0xA5, NGZ_OUTPUT_GUARD, st));
     if (total) {
         NGZ_STAGE_HIP(o, hipEventRecord(o->ev[0], st));
-        auto kernel = o->writer ? (small ? k_agg_json_pack<JS_STAGE_SMALL, JByte> : k_agg_json_pack<JS_STAGE_LARGE, JByte>)
-                                : (small ? k_agg_json_pack<JS_STAGE_SMALL, JAcc> : k_agg_json_pack<JS_STAGE_LARGE, JAcc>);
-        hipLaunchKernelGGL(kernel, dim3(nb), dim3(JS_THREADS), 0, st, A);
+        hipLaunchKernelGGL(use_float ? pack_kernel<true>(small, o->writer != 0) : pack_kernel<false>(small, o->writer != 0), dim3(nb),
+                           dim3(JS_THREADS), 0, st, A);
         NGZ_STAGE_HIP(o, hipGetLastError());
         ++o->launches;
         NGZ_STAGE_HIP(o, hipEventRecord(o->ev[3], st));

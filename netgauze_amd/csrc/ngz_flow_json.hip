@@ -8,8 +8,8 @@
 // fields as items (column, renderer, separator and tag as constant text in a dword-padded pool), uploads
 // the plan in one copy, and runs, whatever the number of slots,
 //   k_fj_dgrams     one thread per datagram: rendered, not OK, or left to the host for its template sets,
-//   k_fj_sets       one thread per data set: its datagram's range of sets; a float template's datagram
-//                   is left to the host,
+//   k_fj_sets       one thread per data set: its datagram's range of sets; the datagram of a template with
+//                   a float the plan did not take (NGZ_FLOW_JSON_OPT_FLOATS 0, float32) is left to the host,
 //   k_fj_tiles      one thread per data set: its tiles, ceil(n / 64), if its datagram is rendered,
 //   a hipcub exclusive scan and k_fj_fill: the tile table (set, first record),
 //   k_fj_size       a wave per tile, a lane per record through the counting writer, a wave sum per tile,
@@ -22,6 +22,9 @@
 //                   into the wave's LDS image, which goes out in 16-byte stores; a record longer than the
 //                   image goes straight out through the byte writer.
 // pack_tile stores its ragged ends by bytes, so the glue and pack passes write disjoint bytes.
+// k_fj_size and k_fj_pack have a second instantiation (FLT) whose renderer knows float64 (put_f64,
+// ngz_f64_dev.h); it is launched in their place only when a slot with rows carries a float item, so a batch
+// without one runs the kernels it ran before there was a float renderer.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
@@ -32,6 +35,7 @@
 
 #include "ngz/flow_json.h"
 #include "ngz_host.h"
+#include "ngz_f64_dev.h"
 #include "ngz_json_dev.h"
 #include "ngz_output_enc.h"
 #include "ngz_stage.h"
@@ -52,7 +56,7 @@ constexpr uint8_t HOW_FLOAT = 3;  // between k_fj_sets and k_fj_dgram_len: NGZ_F
 
 enum : uint8_t {  // put_value / put_field of ngz_json.cpp, case by case
     RD_NULL, RD_U64, RD_I64, RD_BOOL, RD_IP4, RD_IP6, RD_LIST, RD_STRZ, RD_DT_SECS, RD_DT_MS, RD_DT_FRAC, RD_TCP, RD_SUBREG,
-    RD_SUBREG_NESTED, RD_VSTR, RD_VLIST
+    RD_SUBREG_NESTED, RD_VSTR, RD_VLIST, RD_F64
 };
 enum { T_V10_A, T_SEQ, T_V10_DOMAIN, T_V9_A, T_V9_TIME, T_V9_SOURCE, T_SETS, T_DGRAM_TAIL, T_SET_TAIL, T_UNASSIGNED, T_COUNT };
 
@@ -103,9 +107,15 @@ __device__ __forceinline__ bool set_ok(const FArgs &A, const ngz_set_info &si) {
     return si.dgram < A.n_dgrams && si.slot < A.n_slots && (!si.n || (uint64_t)si.rec0 + si.n <= A.slots[si.slot].n_rows);
 }
 
-template <class W>
+template <bool FLT, class W>
 __device__ __forceinline__ void render_value(W &w, const FArgs &A, const FItem &it, uint32_t row, uint32_t *err) {
     const uint8_t *cell = it.col + (uint64_t)row * it.width;
+    if constexpr (FLT) {  // outside the switch: without FLT this function is what it was
+        if (it.rend == RD_F64) {
+            put_f64(w, ld_cell(cell, 8));
+            return;
+        }
+    }
     switch (it.rend) {
     case RD_U64: put_dec(w, ld_cell(cell, it.width)); break;
     case RD_I64: {
@@ -161,13 +171,13 @@ __device__ __forceinline__ void render_value(W &w, const FArgs &A, const FItem &
 }
 
 // Row `row` of slot S as a record of its set, and the comma after it unless it is the set's last
-template <class W>
+template <bool FLT, class W>
 __device__ __forceinline__ void render_record(const FArgs &A, const FSlot &S, uint32_t row, bool last, W &w, uint32_t *err) {
     w.text(A.pool + S.rec_head.off / 4u, S.rec_head.len);
     for (uint32_t i = 0; i < S.n_items; ++i) {
         const FItem &it = A.items[S.item0 + i];
         w.text(A.pool + it.pre.off / 4u, it.pre.len);
-        render_value(w, A, it, row, err);
+        render_value<FLT>(w, A, it, row, err);
         w.text(A.pool + it.suf.off / 4u, it.suf.len);
     }
     w.text(A.pool + S.rec_tail.off / 4u, S.rec_tail.len);
@@ -254,6 +264,7 @@ __global__ __launch_bounds__(FJ_THREADS) void k_fj_fill(const FArgs A) {
     }
 }
 
+template <bool FLT>
 __global__ __launch_bounds__(FJ_THREADS) void k_fj_size(const FArgs A) {
     const uint32_t lane = threadIdx.x & 63u, n_tiles = min(A.tile0[A.n_sets], A.tile_cap);
     uint32_t err = 0;
@@ -263,7 +274,7 @@ __global__ __launch_bounds__(FJ_THREADS) void k_fj_size(const FArgs A) {
         const FSlot &S = A.slots[si.slot];
         const uint32_t cnt = min(FJ_TILE, si.n - tl.first);
         JCount w;
-        if (lane < cnt) render_record(A, S, si.rec0 + tl.first + lane, tl.first + lane + 1u == si.n, w, &err);
+        if (lane < cnt) render_record<FLT>(A, S, si.rec0 + tl.first + lane, tl.first + lane + 1u == si.n, w, &err);
         const uint64_t sum = ngzs::wave_sum(w.n);
         if (lane == 0) A.tile_bytes[t] = (uint32_t)sum;
     }
@@ -345,7 +356,7 @@ __global__ __launch_bounds__(FJ_THREADS) void k_fj_glue_sets(const FArgs A) {
 }
 
 // One wave per block: LDS, not threads, bounds what a CU holds
-template <class WImg>
+template <class WImg, bool FLT>
 __global__ __launch_bounds__(64) void k_fj_pack(const FArgs A, const uint32_t n_tiles) {
     __shared__ __attribute__((aligned(16))) uint8_t img[FJ_IMG + 16];  // pack_tile's
     const uint32_t lane = threadIdx.x;
@@ -357,7 +368,7 @@ __global__ __launch_bounds__(64) void k_fj_pack(const FArgs A, const uint32_t n_
         const uint32_t cnt = min(FJ_TILE, si.n - tl.first), row = si.rec0 + tl.first + lane;
         const bool last = tl.first + lane + 1u == si.n;
         JCount c;
-        if (lane < cnt) render_record(A, S, row, last, c, &err);
+        if (lane < cnt) render_record<FLT>(A, S, row, last, c, &err);
         uint32_t incl = c.n;
 #pragma unroll
         for (int k = 1; k < 64; k <<= 1) {
@@ -365,7 +376,7 @@ __global__ __launch_bounds__(64) void k_fj_pack(const FArgs A, const uint32_t n_
             if (lane >= (uint32_t)k) incl += up;
         }
         ngzenc::pack_tile<FJ_IMG, WImg, JByte>(lane, cnt, A.tile_off[t], incl - c.n, incl, A.out, A.total, img,
-                                               [&](auto &w) { render_record(A, S, row, last, w, &err); });
+                                               [&](auto &w) { render_record<FLT>(A, S, row, last, w, &err); });
     }
     if (err) atomicOr((unsigned int *)&A.counters[C_ERR], err);
 }
@@ -376,6 +387,7 @@ struct ngz_flow_json : ngzs::Stage {
     ngz_flow_json() : Stage(4) {}
     float size_ms = 0, offsets_ms = 0, pack_ms = 0;
     int launches = 0;
+    bool floats = false;                 // NGZ_FLOW_JSON_OPT_FLOATS
     uint64_t n_dgrams = 0, n_bytes = 0;  // the last encode
     bool have = false;
     ngzh::DevBuf<uint8_t> d_in, d_how, d_bytes, d_scan_tmp;  // d_in: slots, items, names, pool, template datagrams
@@ -396,10 +408,11 @@ std::string ie_label(const Spec &s) {
 
 const char *const kScopeNames[] = {nullptr, "System", "Interface", "LineCard", "Cache", "Template"};
 
-// put_field / put_value's choice for field `sp` of column layout `fd`.  *is_float: serde_json's float text,
-// which the device does not render.  false: a column the loaders cannot read.
-bool pick(const Spec &sp, const DevField &fd, Pool &pool, std::vector<JName> &names, FItem *it, std::string *pre, std::string *suf,
-          bool *is_float) {
+// put_field / put_value's choice for field `sp` of column layout `fd`.  *is_float: serde_json's float text
+// where the plan leaves it to the host (float32 always, float64 unless `floats`).  false: a column the
+// loaders cannot read.
+bool pick(const Spec &sp, const DevField &fd, bool floats, Pool &pool, std::vector<JName> &names, FItem *it, std::string *pre,
+          std::string *suf, bool *is_float) {
     const bool int_w = fd.width == 1 || fd.width == 2 || fd.width == 4 || fd.width == 8;
     it->width = fd.width;
     it->rend = RD_NULL;
@@ -425,6 +438,10 @@ bool pick(const Spec &sp, const DevField &fd, Pool &pool, std::vector<JName> &na
                 it->rend = sk == 2 ? RD_SUBREG_NESTED : RD_SUBREG;
                 return int_w;
             }
+        }
+        if (known && sp.dtype == ngzh::DT_float64 && floats) {
+            it->rend = RD_F64;
+            return fd.width == 8;
         }
         if (known && (sp.dtype == ngzh::DT_float32 || sp.dtype == ngzh::DT_float64)) *is_float = true;
         if (known && sp.dtype == ngzh::DT_ipv4Address) it->rend = RD_IP4;
@@ -481,6 +498,23 @@ void ngz_flow_json_destroy(ngz_flow_json *j) {
 
 const char *ngz_flow_json_last_error(ngz_flow_json *j) { return j ? j->last_error.c_str() : "null flow JSON stage"; }
 
+int ngz_flow_json_set_option(ngz_flow_json *j, int opt, int64_t value) {
+    if (!j) return NGZ_E_INVALID;
+    if (opt != NGZ_FLOW_JSON_OPT_FLOATS || (value != 0 && value != 1)) return ngzs::fail(j, NGZ_E_INVALID, "unknown option or value");
+    j->floats = value != 0;
+    return NGZ_OK;
+}
+
+int ngz_flow_json_f64_text(uint64_t bits, char *buf, size_t cap) {
+    uint8_t text[32];  // put_f64 writes at most 24 characters
+    JByte w{text, text + sizeof text};
+    put_f64(w, bits);
+    const size_t n = (size_t)(w.p - text);
+    if (!buf || cap < n) return NGZ_E_INVALID;
+    memcpy(buf, text, n);
+    return (int)n;
+}
+
 int ngz_flow_json_encode(ngz_flow_json *o, ngz_ctx *ctx, const ngz_batch_out *out, ngz_flow_json_stats *stats, void *hip_stream) {
     if (!o || !ctx || !out) return NGZ_E_INVALID;
     if (stats) memset(stats, 0, sizeof *stats);
@@ -504,6 +538,7 @@ int ngz_flow_json_encode(ngz_flow_json *o, ngz_ctx *ctx, const ngz_batch_out *ou
     std::vector<JName> names;
     Pool pool;
     uint64_t n_records = 0;
+    bool use_float = false;  // a slot with rows has a float item: the renderer kernels' float instantiation
     for (uint32_t s = 0; s < S; ++s) {
         const ngz_slot_info &si = out->slots[s];
         const int32_t vi = ctx->slot_version[s];
@@ -526,9 +561,10 @@ int ngz_flow_json_encode(ngz_flow_json *o, ngz_ctx *ctx, const ngz_batch_out *ou
             FItem it{};
             std::string pre, suf;
             bool is_float = false;
-            if (!pick(sp, fd, pool, names, &it, &pre, &suf, &is_float))
+            if (!pick(sp, fd, o->floats, pool, names, &it, &pre, &suf, &is_float))
                 return ngzs::fail(o, NGZ_E_LIMIT, "field " + ie_label(sp) + ": a column of a width the renderers cannot read");
             if (is_float) fs.has_float = 1;
+            if (it.rend == RD_F64 && si.n_records) use_float = true;
             it.col = si.columns ? si.columns + (uint64_t)si.capacity * fd.col_off : nullptr;
             it.pre = pool.add((f == ver.n_scope ? "],\"fields\":[" : f ? "," : "") + pre);
             it.suf = pool.add(suf);
@@ -626,7 +662,7 @@ int ngz_flow_json_encode(ngz_flow_json *o, ngz_ctx *ctx, const ngz_batch_out *ou
         ++o->launches;
         NGZ_STAGE_HIP(o, launch(k_fj_fill, blocks(NS), FJ_THREADS, A));
         const uint32_t nb = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((tile_cap + 3) / 4, (uint64_t)o->n_cus * 16));
-        NGZ_STAGE_HIP(o, launch(k_fj_size, nb, FJ_THREADS, A));
+        NGZ_STAGE_HIP(o, launch(use_float ? k_fj_size<true> : k_fj_size<false>, nb, FJ_THREADS, A));
     }
     NGZ_STAGE_HIP(o, hipEventRecord(o->ev[1], st));
     if (NS) NGZ_STAGE_HIP(o, launch(k_fj_set_len, blocks(NS), FJ_THREADS, A));
@@ -657,7 +693,7 @@ int ngz_flow_json_encode(ngz_flow_json *o, ngz_ctx *ctx, const ngz_batch_out *ou
         if (NS) NGZ_STAGE_HIP(o, launch(k_fj_glue_sets, blocks(NS), FJ_THREADS, A));
         if (n_tiles) {
             const uint32_t nb = (uint32_t)std::min<uint64_t>(n_tiles, (uint64_t)o->n_cus * 16);
-            NGZ_STAGE_HIP(o, launch(k_fj_pack<JAcc>, nb, 64u, A, n_tiles));
+            NGZ_STAGE_HIP(o, launch(use_float ? k_fj_pack<JAcc, true> : k_fj_pack<JAcc, false>, nb, 64u, A, n_tiles));
         }
         NGZ_STAGE_HIP(o, hipEventRecord(o->ev[3], st));
     }

@@ -45,18 +45,18 @@ struct JCount {
 struct JByte {  // the plain byte writer; nothing is stored at or past `end`
     static constexpr bool counting = false;
     uint8_t *p, *end;
-    __device__ __forceinline__ void put(uint32_t b) {
+    __host__ __device__ __forceinline__ void put(uint32_t b) {
         if (p < end) *p = (uint8_t)b;
         ++p;
     }
-    __device__ __forceinline__ void push(uint32_t d, uint32_t k) {
+    __host__ __device__ __forceinline__ void push(uint32_t d, uint32_t k) {
         for (uint32_t i = 0; i < k; ++i) put(d >> (8u * i));
     }
-    __device__ __forceinline__ void text(const uint32_t *s, uint32_t len) {
+    __host__ __device__ __forceinline__ void text(const uint32_t *s, uint32_t len) {
         const uint8_t *b = (const uint8_t *)s;
         for (uint32_t i = 0; i < len; ++i) put(b[i]);
     }
-    __device__ __forceinline__ void finish() {}
+    __host__ __device__ __forceinline__ void finish() {}
 };
 // The accumulating writer over [begin, end) of an LDS image.  acc holds `fill` < 4 pending bytes in its
 // low end; whatever comes in is shifted up by 8 * fill and ORed in, and each time four bytes are

@@ -276,7 +276,9 @@ class AggFlowJson:
 
     def set_option(self, opt, value):
         """ngz_agg_json_set_option: NGZ_AGG_JSON_OPT_WRITER 0 accumulating | 1 byte writer (how the pack pass
-        runs, never what it writes)."""
+        runs, never what it writes); NGZ_AGG_JSON_OPT_FLOATS 0 a float key or aggregated field is refused
+        (NGZ_OUTPUT_E_UNSUPPORTED) | 1 a float64 one is rendered on the device (what an encode accepts;
+        float32 stays refused)."""
         self._check(lib().ngz_agg_json_set_option(self._h, opt, value))
 
     def encode(self, aggregator, raw, shard_id=0, seq0=0, export_time_ms=0, stream=None):
@@ -345,6 +347,21 @@ class FlowJson:
         if rc < 0:
             raise OutputError("%s (%d)" % (lib().ngz_flow_json_last_error(self._h).decode(), rc), rc)
         return rc
+
+    def set_option(self, opt, value):
+        """ngz_flow_json_set_option: NGZ_FLOW_JSON_OPT_FLOATS 0 (default) the datagrams of a template with a
+        float64 field are left to the host (HOST, `left_float`) | 1 they are rendered on the device."""
+        self._check(lib().ngz_flow_json_set_option(self._h, opt, value))
+
+    @staticmethod
+    def f64_text(bits):
+        """serde_json's text of the float64 with bit pattern `bits` (ngz_flow_json_f64_text: the device's
+        routine compiled for the host; no HIP call)."""
+        buf = ctypes.create_string_buffer(32)
+        n = lib().ngz_flow_json_f64_text(bits, buf, 32)
+        if n < 0:
+            raise OutputError("ngz_flow_json_f64_text failed (%d)" % n, n)
+        return buf.raw[:n].decode()
 
     def encode(self, batch, stream=None):
         """Render the codec's latest DecodedBatch; this encode's counters.  The batch's input must still be

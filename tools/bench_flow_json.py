@@ -11,7 +11,13 @@ compared with; `host_over_device` scales it to --records by its per-record time.
 ngz_agg_json_encode to set beside this one comes from tools/bench_agg_json.py, run next to it.  Prints one
 JSON line; --out appends a summary line.
 
+--floats: the same batch with T20's packetDeltaCount (IE 2, 8 bytes) replaced by samplingProbability (IE 311,
+float64) in template 257: seeded finite bit patterns of either sign with the exponent field anywhere below
+1024, so nearly every value prints 16 or 17 digits and an exponent, the longest texts there are.  The stage runs
+with NGZ_FLOW_JSON_OPT_FLOATS 1; ngz_batch_json over the same batch is what those datagrams cost without it.
+
     python tools/bench_flow_json.py --records 1000000 --steps 20 --warmup 3
+    python tools/bench_flow_json.py --records 1000000 --steps 20 --warmup 3 --floats
 """
 import argparse
 import json
@@ -24,10 +30,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def decode(codec, synth, n):
-    _offs, rec_len = synth.field_offsets(synth.T20)
+def decode(codec, synth, n, floats=False):
+    offs, rec_len = synth.field_offsets(synth.T20)
     rec = synth.t20_records(n, device="cuda")
-    buf, moffs, mlens = synth.ipfix_data_stream(rec, rec_len)
+    if floats:  # the top exponent bit cleared: every pattern is finite
+        rec[:, offs[[f for f, _ in synth.T20].index(2)]] &= 0xBF
+    buf, moffs, mlens = synth.ipfix_data_stream(rec, rec_len, tid=synth.T20_ID + int(floats))
     return codec.decode_batch(buf, moffs, mlens), (buf, moffs, mlens)
 
 
@@ -37,6 +45,7 @@ def main():
     ap.add_argument("--host-records", type=int, default=1_000_000, help="records of the batch ngz_batch_json renders")
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--floats", action="store_true", help="T20 with samplingProbability in place of packetDeltaCount, the option on")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.steps < 5:
@@ -47,10 +56,16 @@ def main():
     from netgauze_amd.output import FlowJson
     assert torch.cuda.is_available(), "bench_flow_json needs a HIP device"
     codec = FlowInfoCodec(0, specialize=True)
-    codec.decode_datagrams([synth.template_message()])
     fj, res = FlowJson(), {"records": args.records, "steps": args.steps}
+    if args.floats:
+        from netgauze_amd import _lib
+        codec.decode_datagrams([synth.template_message(synth.T20_ID + 1, [(311, 8) if f == 2 else (f, ln) for f, ln in synth.T20])])
+        fj.set_option(_lib.NGZ_FLOW_JSON_OPT_FLOATS, 1)
+        res["variant"] = "samplingProbability"
+    else:
+        codec.decode_datagrams([synth.template_message()])
     n_host = min(args.records, args.host_records)
-    batch, keep = decode(codec, synth, n_host)  # the host function's batch, checked line for line
+    batch, keep = decode(codec, synth, n_host, args.floats)  # the host function's batch, checked line for line
     stats = fj.encode(batch)
     data, offs, how = fj.result()
     t0 = time.perf_counter()
@@ -61,7 +76,7 @@ def main():
     res.update(host_records=n_host, batch_json_host_ms=round(host_ms, 1), batch_json_host_us_per_record=round(host_ms * 1e3 / n_host, 3))
     if n_host != args.records:
         del batch, keep, host, data
-        batch, keep = decode(codec, synth, args.records)
+        batch, keep = decode(codec, synth, args.records, args.floats)
     ms, wall = [], []
     for step in range(args.warmup + args.steps):
         t0 = time.perf_counter()
