@@ -6,15 +6,16 @@
 // consecutive rows of the slot's columns, so a lane-per-row load coalesces, and consecutive in the output,
 // so a wave's LDS image (pack_tile, ngz_output_enc.h) holds them.  Per encode the host lists every slot's
 // fields as items (column, renderer, separator and tag as constant text in a dword-padded pool), uploads
-// the plan in one copy, and runs, whatever the number of slots,
-//   k_fj_dgrams     one thread per datagram: rendered, not OK, or left to the host for its template sets,
-//   k_fj_sets       one thread per data set: its datagram's range of sets; the datagram of a template with
+// the plan in one copy, and runs, whatever the number of slots, the passes of ngz_msg_stream.h (shared with
+// ngz_wire.hip; FStream below says what is this stage's in them) around its own, the k_fj_ ones:
+//   k_dgrams        one thread per datagram: rendered, not OK, or left to the host for its template sets,
+//   k_sets          one thread per data set: its datagram's range of sets; the datagram of a template with
 //                   a float the plan did not take (NGZ_FLOW_JSON_OPT_FLOATS 0, float32) is left to the host,
-//   k_fj_tiles      one thread per data set: its tiles, ceil(n / 64), if its datagram is rendered,
-//   a hipcub exclusive scan and k_fj_fill: the tile table (set, first record),
+//   k_tiles         one thread per data set: its tiles, ceil(n / 64), if its datagram is rendered,
+//   a hipcub exclusive scan and k_fill: the tile table (set, first record),
 //   k_fj_size       a wave per tile, a lane per record through the counting writer, a wave sum per tile,
-//   k_fj_set_len    one thread per set: head, its tiles, tail,
-//   k_fj_dgram_len  one thread per datagram: head, sets, commas, tail; the stats,
+//   k_set_len       one thread per set: head, its tiles, tail,
+//   k_dgram_len     one thread per datagram: head, sets, commas, tail; the stats,
 //   a hipcub exclusive scan: the u64 offsets,
 //   k_fj_glue_dgrams / k_fj_glue_sets  the same two walks downwards: every set's and tile's output offset,
 //                   and the glue itself, written straight out by bytes,
@@ -26,7 +27,6 @@
 // ngz_f64_dev.h); it is launched in their place only when a slot with rows carries a float item, so a batch
 // without one runs the kernels it ran before there was a float renderer.
 #include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
 
 #include <algorithm>
 #include <cstring>
@@ -37,22 +37,21 @@
 #include "ngz_host.h"
 #include "ngz_f64_dev.h"
 #include "ngz_json_dev.h"
+#include "ngz_msg_stream.h"
 #include "ngz_output_enc.h"
-#include "ngz_stage.h"
 
 namespace {
 
 using namespace ngzjson;
+using namespace ngzms;
 using ngzrow::align256;
 
-constexpr uint32_t FJ_THREADS = 256;
-constexpr uint32_t FJ_TILE = 64;
+constexpr uint32_t FJ_THREADS = THREADS;
 // A wave's image, and 16 of slack for the output's misalignment: §2i's.  Nothing is staged here (a lane
 // loads its own row's cells from the columns), so a block's LDS is the image: 30 KB, five blocks per CU.
 constexpr uint32_t FJ_IMG = 30704;
-constexpr uint32_t ERR_SETS = 1, ERR_VLEN = 2, ERR_TILES = 4;
-constexpr uint32_t C_ERR = 0, C_LINES = 1, C_TEMPLATE = 2, C_FLOAT = 3, C_NOT_OK = 4, C_COUNT = 5;
-constexpr uint8_t HOW_FLOAT = 3;  // between k_fj_sets and k_fj_dgram_len: NGZ_FLOW_JSON_HOST for a float field
+constexpr uint32_t C_LINES = 1, C_TEMPLATE = 2, C_FLOAT = 3, C_NOT_OK = 4;  // ngz_flow_json_stats' order
+constexpr uint8_t HOW_FLOAT = 3;  // between k_sets and k_dgram_len: NGZ_FLOW_JSON_HOST for a float field
 
 enum : uint8_t {  // put_value / put_field of ngz_json.cpp, case by case
     RD_NULL, RD_U64, RD_I64, RD_BOOL, RD_IP4, RD_IP6, RD_LIST, RD_STRZ, RD_DT_SECS, RD_DT_MS, RD_DT_FRAC, RD_TCP, RD_SUBREG,
@@ -72,40 +71,13 @@ struct FSlot {
     uint32_t n_rows, has_float;
     JText rec_head, rec_tail, set_head;  // {"scope_fields":[  |  ]}  |  {"Data":{"id":<template id>,"records":[
 };
-struct FTile {
-    uint32_t set, first;  // records [first, first + 64) of the set, as far as it has them
-};
-struct FArgs {  // passed by value
+struct FArgs : Layout {  // passed by value
     const FSlot *slots;
     const FItem *items;
     const JName *names;
     const uint32_t *pool;
-    const uint32_t *host_dgrams;  // the datagrams with (options) template sets, ascending
     JText fixed[T_COUNT];
-    const ngz_set_info *sets;
-    const ngz_dgram_hdr *hdr;
-    const uint8_t *in;  // the batch input
-    unsigned long long in_size;
-    uint32_t n_host, n_sets, n_dgrams, n_slots, tile_cap;
-    uint8_t *how;
-    uint32_t *dset0, *dset1;  // per datagram: its sets [dset0, dset1)
-    uint32_t *ntiles, *tile0;  // per set, and one more: tile0[n_sets] is the number of tiles
-    FTile *tiles;
-    uint32_t *tile_bytes;
-    unsigned long long *tile_off, *set_len, *set_off, *dlen, *offs;
-    uint8_t *out;
-    unsigned long long total;
-    unsigned long long *counters;
 };
-
-__device__ __forceinline__ uint64_t ld_cell(const uint8_t *p, uint32_t w) {  // p: aligned to w
-    return w == 8 ? *(const uint64_t *)p : w == 4 ? *(const uint32_t *)p : w == 2 ? *(const uint16_t *)p : *p;
-}
-
-// A set inside the batch's tables
-__device__ __forceinline__ bool set_ok(const FArgs &A, const ngz_set_info &si) {
-    return si.dgram < A.n_dgrams && si.slot < A.n_slots && (!si.n || (uint64_t)si.rec0 + si.n <= A.slots[si.slot].n_rows);
-}
 
 template <bool FLT, class W>
 __device__ __forceinline__ void render_value(W &w, const FArgs &A, const FItem &it, uint32_t row, uint32_t *err) {
@@ -212,113 +184,37 @@ __device__ __forceinline__ void render_head(const FArgs &A, const ngz_dgram_hdr 
 // ---------------------------------------------------------------------------------------------
 // kernels
 // ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(FJ_THREADS) void k_fj_dgrams(const FArgs A) {
-    const uint32_t d = blockIdx.x * FJ_THREADS + threadIdx.x;
-    if (d >= A.n_dgrams) return;
-    uint8_t how = A.hdr[d].status == NGZ_DG_OK ? NGZ_FLOW_JSON_LINE : NGZ_FLOW_JSON_NONE;
-    uint32_t lo = 0, hi = A.n_host;
-    while (lo < hi) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (A.host_dgrams[mid] < d) lo = mid + 1;
-        else hi = mid;
+// What is this stage's in the shared passes (ngz_msg_stream.h)
+struct FStream {
+    using Args = FArgs;
+    static __device__ __forceinline__ int sets_how(const FSlot &S, const uint8_t &how) { return S.has_float && how == HOW_WRITTEN ? HOW_FLOAT : -1; }
+    static __device__ __forceinline__ void fill_tile(const FArgs &, const FSlot &, uint32_t, uint32_t, uint32_t) {}  // k_fj_size sizes every tile
+    static __device__ __forceinline__ unsigned long long set_len(const FArgs &A, const ngz_set_info &si, unsigned long long tiles) {
+        return A.slots[si.slot].set_head.len + A.fixed[T_SET_TAIL].len + tiles;
     }
-    if (how == NGZ_FLOW_JSON_LINE && lo < A.n_host && A.host_dgrams[lo] == d) how = NGZ_FLOW_JSON_HOST;
-    A.how[d] = how;
-    A.dset0[d] = A.dset1[d] = 0;
-}
-
-__global__ __launch_bounds__(FJ_THREADS) void k_fj_sets(const FArgs A) {
-    const uint32_t s = blockIdx.x * FJ_THREADS + threadIdx.x;
-    if (s >= A.n_sets) return;
-    const ngz_set_info si = A.sets[s];
-    if (!set_ok(A, si)) {
-        atomicOr((unsigned int *)&A.counters[C_ERR], ERR_SETS);
-        return;
+    static __device__ __forceinline__ unsigned long long dgram_frame(const FArgs &A, const ngz_dgram_hdr &h, uint32_t n_sets) {
+        JCount w;
+        render_head(A, h, w);
+        return w.n + A.fixed[T_DGRAM_TAIL].len + (n_sets ? n_sets - 1u : 0u);  // a comma between two sets
     }
-    if (s == 0 || A.sets[s - 1].dgram != si.dgram) A.dset0[si.dgram] = s;  // the sets are in stream order
-    if (s + 1 == A.n_sets || A.sets[s + 1].dgram != si.dgram) A.dset1[si.dgram] = s + 1;
-    if (A.slots[si.slot].has_float && A.how[si.dgram] == NGZ_FLOW_JSON_LINE) A.how[si.dgram] = HOW_FLOAT;
-}
-
-__global__ __launch_bounds__(FJ_THREADS) void k_fj_tiles(const FArgs A) {
-    const uint32_t s = blockIdx.x * FJ_THREADS + threadIdx.x;
-    if (s > A.n_sets) return;
-    uint32_t n = 0;
-    if (s < A.n_sets) {
-        const ngz_set_info si = A.sets[s];
-        if (set_ok(A, si) && A.how[si.dgram] == NGZ_FLOW_JSON_LINE) n = (si.n + FJ_TILE - 1) / FJ_TILE;
+    static __device__ __forceinline__ uint32_t counter(const FArgs &A, uint32_t d, uint8_t how) {  // C_LINES + this
+        if (how == HOW_FLOAT) A.how[d] = HOW_HOST;
+        return how == HOW_WRITTEN ? 0u : how == HOW_HOST ? 1u : how == HOW_FLOAT ? 2u : 3u;
     }
-    A.ntiles[s] = n;  // ntiles[n_sets] = 0: the scan's last item
-}
-
-__global__ __launch_bounds__(FJ_THREADS) void k_fj_fill(const FArgs A) {
-    const uint32_t s = blockIdx.x * FJ_THREADS + threadIdx.x;
-    if (s >= A.n_sets) return;
-    const uint32_t t0 = A.tile0[s], n = A.ntiles[s];
-    for (uint32_t t = 0; t < n; ++t) {
-        if (t0 + t >= A.tile_cap || t0 + t < t0) {
-            atomicOr((unsigned int *)&A.counters[C_ERR], ERR_TILES);
-            break;
-        }
-        A.tiles[t0 + t] = FTile{s, t * FJ_TILE};
-    }
-}
+};
 
 template <bool FLT>
 __global__ __launch_bounds__(FJ_THREADS) void k_fj_size(const FArgs A) {
     const uint32_t lane = threadIdx.x & 63u, n_tiles = min(A.tile0[A.n_sets], A.tile_cap);
     uint32_t err = 0;
     for (uint32_t t = blockIdx.x * (FJ_THREADS / 64u) + (threadIdx.x >> 6); t < n_tiles; t += gridDim.x * (FJ_THREADS / 64u)) {
-        const FTile tl = A.tiles[t];
-        const ngz_set_info si = A.sets[tl.set];
-        const FSlot &S = A.slots[si.slot];
-        const uint32_t cnt = min(FJ_TILE, si.n - tl.first);
+        const TileRows tr = tile_rows(A, t);
         JCount w;
-        if (lane < cnt) render_record<FLT>(A, S, si.rec0 + tl.first + lane, tl.first + lane + 1u == si.n, w, &err);
+        if (lane < tr.cnt) render_record<FLT>(A, A.slots[tr.si.slot], tr.row0 + lane, tr.first + lane + 1u == tr.si.n, w, &err);
         const uint64_t sum = ngzs::wave_sum(w.n);
         if (lane == 0) A.tile_bytes[t] = (uint32_t)sum;
     }
     if (err) atomicOr((unsigned int *)&A.counters[C_ERR], err);
-}
-
-__global__ __launch_bounds__(FJ_THREADS) void k_fj_set_len(const FArgs A) {
-    const uint32_t s = blockIdx.x * FJ_THREADS + threadIdx.x;
-    if (s >= A.n_sets) return;
-    const ngz_set_info si = A.sets[s];
-    unsigned long long len = 0;
-    if (set_ok(A, si) && A.how[si.dgram] == NGZ_FLOW_JSON_LINE) {
-        len = A.slots[si.slot].set_head.len + A.fixed[T_SET_TAIL].len;
-        const uint32_t t1 = min(A.tile0[s + 1], A.tile_cap);
-        for (uint32_t t = A.tile0[s]; t < t1; ++t) len += A.tile_bytes[t];
-    }
-    A.set_len[s] = len;
-}
-
-__global__ __launch_bounds__(FJ_THREADS) void k_fj_dgram_len(const FArgs A) {
-    __shared__ unsigned long long acc[4];
-    const uint32_t d = blockIdx.x * FJ_THREADS + threadIdx.x;
-    uint64_t c[4] = {0, 0, 0, 0};  // lines, left for templates, left for floats, not OK
-    if (d < A.n_dgrams) {
-        unsigned long long len = 0;
-        const uint8_t how = A.how[d];
-        if (how == NGZ_FLOW_JSON_LINE) {
-            JCount w;
-            render_head(A, A.hdr[d], w);
-            const uint32_t s0 = A.dset0[d], s1 = min(A.dset1[d], A.n_sets);
-            len = w.n + A.fixed[T_DGRAM_TAIL].len + (s1 > s0 ? s1 - s0 - 1u : 0u);  // a comma between two sets
-            for (uint32_t s = s0; s < s1; ++s) len += A.set_len[s];
-            c[0] = 1;
-        } else if (how == HOW_FLOAT) {
-            A.how[d] = NGZ_FLOW_JSON_HOST;
-            c[2] = 1;
-        } else {
-            c[how == NGZ_FLOW_JSON_HOST ? 1 : 3] = 1;
-        }
-        A.dlen[d] = len;
-        if (d == 0) A.dlen[A.n_dgrams] = 0;  // the scan's last item
-    }
-    unsigned long long *const dst[4] = {&A.counters[C_LINES], &A.counters[C_TEMPLATE], &A.counters[C_FLOAT], &A.counters[C_NOT_OK]};
-    ngzs::block_add<4>(acc, c, dst);
 }
 
 // The datagram's head, the commas between its sets and its closing text; where each of its sets starts
@@ -342,7 +238,7 @@ __global__ __launch_bounds__(FJ_THREADS) void k_fj_glue_sets(const FArgs A) {
     const uint32_t s = blockIdx.x * FJ_THREADS + threadIdx.x;
     if (s >= A.n_sets) return;
     const ngz_set_info si = A.sets[s];
-    if (A.how[si.dgram] != NGZ_FLOW_JSON_LINE) return;
+    if (!set_ok(A, si) || A.how[si.dgram] != NGZ_FLOW_JSON_LINE) return;
     const JText head = A.slots[si.slot].set_head;
     const unsigned long long o0 = A.set_off[s], o1 = min(o0 + A.set_len[s], A.total);
     JByte w{A.out + o0, A.out + o1};
@@ -362,20 +258,14 @@ __global__ __launch_bounds__(64) void k_fj_pack(const FArgs A, const uint32_t n_
     const uint32_t lane = threadIdx.x;
     uint32_t err = 0;
     for (uint32_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
-        const FTile tl = A.tiles[t];
-        const ngz_set_info si = A.sets[tl.set];
-        const FSlot &S = A.slots[si.slot];
-        const uint32_t cnt = min(FJ_TILE, si.n - tl.first), row = si.rec0 + tl.first + lane;
-        const bool last = tl.first + lane + 1u == si.n;
+        const TileRows tr = tile_rows(A, t);
+        const FSlot &S = A.slots[tr.si.slot];
+        const uint32_t row = tr.row0 + lane;
+        const bool last = tr.first + lane + 1u == tr.si.n;
         JCount c;
-        if (lane < cnt) render_record<FLT>(A, S, row, last, c, &err);
-        uint32_t incl = c.n;
-#pragma unroll
-        for (int k = 1; k < 64; k <<= 1) {
-            const uint32_t up = __shfl_up(incl, k, 64);
-            if (lane >= (uint32_t)k) incl += up;
-        }
-        ngzenc::pack_tile<FJ_IMG, WImg, JByte>(lane, cnt, A.tile_off[t], incl - c.n, incl, A.out, A.total, img,
+        if (lane < tr.cnt) render_record<FLT>(A, S, row, last, c, &err);
+        const uint32_t incl = wave_incl_scan(c.n);
+        ngzenc::pack_tile<FJ_IMG, WImg, JByte>(lane, tr.cnt, A.tile_off[t], incl - c.n, incl, A.out, A.total, img,
                                                [&](auto &w) { render_record<FLT>(A, S, row, last, w, &err); });
     }
     if (err) atomicOr((unsigned int *)&A.counters[C_ERR], err);
@@ -383,19 +273,9 @@ __global__ __launch_bounds__(64) void k_fj_pack(const FArgs A, const uint32_t n_
 
 }  // namespace
 
-struct ngz_flow_json : ngzs::Stage {
-    ngz_flow_json() : Stage(4) {}
-    float size_ms = 0, offsets_ms = 0, pack_ms = 0;
-    int launches = 0;
-    bool floats = false;                 // NGZ_FLOW_JSON_OPT_FLOATS
-    uint64_t n_dgrams = 0, n_bytes = 0;  // the last encode
-    bool have = false;
-    ngzh::DevBuf<uint8_t> d_in, d_how, d_bytes, d_scan_tmp;  // d_in: slots, items, names, pool, template datagrams
-    ngzh::DevBuf<uint32_t> d_u32;                            // dset0, dset1, ntiles, tile0, tile_bytes
-    ngzh::DevBuf<FTile> d_tiles;
-    ngzh::DevBuf<unsigned long long> d_u64, d_offs, d_counters;  // d_u64: tile_off, set_len, set_off, dlen
-    ngzs::PinnedBuf<uint8_t> h_in;
-    ngzs::PinnedBuf<unsigned long long> h_back;  // the counters, the total, the tiles
+struct ngz_flow_json : ngzms::MsgStage {  // its plan in d_in: slots, items, names, pool
+    ngz_flow_json() : MsgStage("flow JSON") {}
+    bool floats = false;  // NGZ_FLOW_JSON_OPT_FLOATS
 };
 
 namespace {
@@ -461,8 +341,6 @@ bool pick(const Spec &sp, const DevField &fd, bool floats, Pool &pool, std::vect
     return true;  // a kind put_value prints as null
 }
 
-uint32_t blocks(uint64_t items) { return (uint32_t)((items + FJ_THREADS - 1) / FJ_THREADS); }
-
 }  // namespace
 
 extern "C" {
@@ -483,15 +361,7 @@ void ngz_flow_json_destroy(ngz_flow_json *j) {
     if (!j) return;
     if (j->device_ready) {
         hipSetDevice(j->device);
-        j->d_in.release();
-        j->d_how.release();
-        j->d_bytes.release();
-        j->d_scan_tmp.release();
-        j->d_u32.release();
-        j->d_tiles.release();
-        j->d_u64.release();
-        j->d_offs.release();
-        j->d_counters.release();
+        j->release_device();
     }
     delete j;
 }
@@ -518,15 +388,8 @@ int ngz_flow_json_f64_text(uint64_t bits, char *buf, size_t cap) {
 int ngz_flow_json_encode(ngz_flow_json *o, ngz_ctx *ctx, const ngz_batch_out *out, ngz_flow_json_stats *stats, void *hip_stream) {
     if (!o || !ctx || !out) return NGZ_E_INVALID;
     if (stats) memset(stats, 0, sizeof *stats);
-    o->have = false;
-    o->n_dgrams = o->n_bytes = 0;
-    o->launches = 0;
-    o->size_ms = o->offsets_ms = o->pack_ms = 0;
-    if (int rc = ngzs::check_ctx(o, ctx)) return rc;
+    if (int rc = ngzms::begin(o, ctx, out)) return rc;
     const uint32_t S = out->n_slots, D = out->n_dgrams, NS = out->n_sets;
-    if (!ngzs::slot_table_ok(out) || S != ctx->slot_version.size() || D != ctx->last_in.n)
-        return ngzs::fail(o, NGZ_E_INVALID, "slot table: `out` is not the context's last decode");
-    if (NS && !out->sets) return ngzs::fail(o, NGZ_E_INVALID, "no set table");
     if (!D) {  // no datagram: no kernel
         o->have = true;
         return NGZ_OK;
@@ -541,14 +404,10 @@ int ngz_flow_json_encode(ngz_flow_json *o, ngz_ctx *ctx, const ngz_batch_out *ou
     bool use_float = false;  // a slot with rows has a float item: the renderer kernels' float instantiation
     for (uint32_t s = 0; s < S; ++s) {
         const ngz_slot_info &si = out->slots[s];
-        const int32_t vi = ctx->slot_version[s];
-        if (vi < 0 || (size_t)vi >= ctx->versions.size()) return ngzs::fail(o, NGZ_E_INVALID, "slot table: `out` is not the context's last decode");
-        const ngzh::Version &ver = ctx->versions[vi];
+        const ngzh::Version *pv;
+        if (int rc = ngzms::slot_version(o, ctx, out, s, &pv)) return rc;
+        const ngzh::Version &ver = *pv;
         const uint32_t nf = (uint32_t)ver.specs.size();
-        if (nf > ver.fields.size()) return ngzs::fail(o, NGZ_E_INVALID, "a template without its column layout");
-        // every column starts at a multiple of 16 bytes: a cell is aligned to its width
-        if (si.n_records && (!si.columns || ((uintptr_t)si.columns & 15) || (si.capacity & 15) || si.capacity < si.n_records))
-            return ngzs::fail(o, NGZ_E_LIMIT, "unexpected column block alignment");
         FSlot &fs = slots[s];
         fs = FSlot{};
         fs.item0 = (uint32_t)items.size();
@@ -587,157 +446,57 @@ int ngz_flow_json_encode(ngz_flow_json *o, ngz_ctx *ctx, const ngz_batch_out *ou
     A.fixed[T_SET_TAIL] = pool.add("]}}");
     A.fixed[T_UNASSIGNED] = pool.add("{\"Unassigned\":");
     pool.b.resize(pool.b.size() + 4, 0);
-    std::vector<uint32_t> host_dgrams;  // (datagram, set position) order: ascending
-    for (const ngzh::TemplateSetJson &t : ctx->tmpl_sets)
-        if (host_dgrams.empty() || host_dgrams.back() != t.dgram) host_dgrams.push_back(t.dgram);
-    const uint64_t tile_cap = n_records / FJ_TILE + NS + 1;  // a set's last tile may be short
-    if (tile_cap >> 31 || pool.b.size() >> 31) return ngzs::fail(o, NGZ_E_LIMIT, "batch too large");
+    if (pool.b.size() >> 31) return ngzs::fail(o, NGZ_E_LIMIT, "batch too large");
 
     const uint64_t items_at = align256(slots.size() * sizeof(FSlot)), names_at = items_at + align256(items.size() * sizeof(FItem));
-    const uint64_t pool_at = names_at + align256(names.size() * sizeof(JName)), host_at = pool_at + align256(pool.b.size());
-    const uint64_t in_bytes = host_at + align256(host_dgrams.size() * sizeof(uint32_t)) + 256;
-    if (int rc = ngzs::device_init(o)) return rc;
-    NGZ_STAGE_HIP(o, hipSetDevice(o->device));
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
-    size_t scan_a = 0, scan_b = 0;
-    if (hipcub::DeviceScan::ExclusiveSum(nullptr, scan_a, (const uint32_t *)nullptr, (uint32_t *)nullptr, (int)(NS + 1), st) != hipSuccess ||
-        hipcub::DeviceScan::ExclusiveSum(nullptr, scan_b, (const unsigned long long *)nullptr, (unsigned long long *)nullptr, (int)(D + 1), st) !=
-            hipSuccess)
-        return ngzs::fail(o, NGZ_E_DEVICE, "scan temp size");
-    const size_t scan_bytes = std::max(scan_a, scan_b);
-    const uint64_t n_u32 = 2ull * D + 2ull * (NS + 1) + tile_cap, n_u64 = tile_cap + 2ull * NS + D + 1;
-    if (o->h_in.reserve(in_bytes) || o->d_in.ensure(in_bytes) || o->d_how.ensure(D) || o->d_u32.ensure(n_u32) || o->d_tiles.ensure(tile_cap) ||
-        o->d_u64.ensure(n_u64) || o->d_offs.ensure(D + 1) || o->d_counters.ensure(C_COUNT) || o->d_scan_tmp.ensure(scan_bytes + 1) ||
-        o->h_back.reserve(C_COUNT + 2))
-        return ngzs::fail(o, NGZ_E_NOMEM, "flow JSON buffers");
+    const uint64_t pool_at = names_at + align256(names.size() * sizeof(JName)), plan_bytes = pool_at + align256(pool.b.size());
+    if (int rc = carve(o, ctx, out, hip_stream, plan_bytes, n_records, &A)) return rc;
     uint8_t *h = o->h_in.p;
-    memset(h, 0, in_bytes);
     if (S) memcpy(h, slots.data(), slots.size() * sizeof(FSlot));
     if (!items.empty()) memcpy(h + items_at, items.data(), items.size() * sizeof(FItem));
     if (!names.empty()) memcpy(h + names_at, names.data(), names.size() * sizeof(JName));
     memcpy(h + pool_at, pool.b.data(), pool.b.size());
-    if (!host_dgrams.empty()) memcpy(h + host_at, host_dgrams.data(), host_dgrams.size() * sizeof(uint32_t));
-
     A.slots = (const FSlot *)o->d_in.p;
     A.items = (const FItem *)(o->d_in.p + items_at);
     A.names = (const JName *)(o->d_in.p + names_at);
     A.pool = (const uint32_t *)(o->d_in.p + pool_at);
-    A.host_dgrams = (const uint32_t *)(o->d_in.p + host_at);
-    A.n_host = (uint32_t)host_dgrams.size();
-    A.sets = out->sets;
-    A.hdr = out->dgrams;
-    A.in = ctx->last_in.bytes;
-    A.in_size = ctx->last_in.bytes_size;
-    A.n_sets = NS;
-    A.n_dgrams = D;
-    A.n_slots = S;
-    A.tile_cap = (uint32_t)tile_cap;
-    A.how = o->d_how.p;
-    A.dset0 = o->d_u32.p;
-    A.dset1 = A.dset0 + D;
-    A.ntiles = A.dset1 + D;
-    A.tile0 = A.ntiles + NS + 1;
-    A.tile_bytes = A.tile0 + NS + 1;
-    A.tiles = o->d_tiles.p;
-    A.tile_off = o->d_u64.p;
-    A.set_len = A.tile_off + tile_cap;
-    A.set_off = A.set_len + NS;
-    A.dlen = A.set_off + NS;
-    A.offs = o->d_offs.p;
-    A.counters = o->d_counters.p;
 
-    NGZ_STAGE_HIP(o, hipMemcpyAsync(o->d_in.p, h, in_bytes, hipMemcpyHostToDevice, st));
-    NGZ_STAGE_HIP(o, hipMemsetAsync(o->d_counters.p, 0, C_COUNT * sizeof(unsigned long long), st));
-    NGZ_STAGE_HIP(o, hipEventRecord(o->ev[0], st));
-    auto launch = [&](auto kernel, uint32_t nb, uint32_t threads, auto... args) {
-        hipLaunchKernelGGL(kernel, dim3(nb), dim3(threads), 0, st, args...);
-        ++o->launches;
-        return hipGetLastError();
-    };
-    NGZ_STAGE_HIP(o, launch(k_fj_dgrams, blocks(D), FJ_THREADS, A));
+    if (int rc = run_tiles<FStream>(o, A)) return rc;
     if (NS) {
-        NGZ_STAGE_HIP(o, launch(k_fj_sets, blocks(NS), FJ_THREADS, A));
-        NGZ_STAGE_HIP(o, launch(k_fj_tiles, blocks((uint64_t)NS + 1), FJ_THREADS, A));
-        NGZ_STAGE_HIP(o, hipcub::DeviceScan::ExclusiveSum(o->d_scan_tmp.p, scan_a, (const uint32_t *)A.ntiles, A.tile0, (int)(NS + 1), st));
-        ++o->launches;
-        NGZ_STAGE_HIP(o, launch(k_fj_fill, blocks(NS), FJ_THREADS, A));
-        const uint32_t nb = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((tile_cap + 3) / 4, (uint64_t)o->n_cus * 16));
-        NGZ_STAGE_HIP(o, launch(use_float ? k_fj_size<true> : k_fj_size<false>, nb, FJ_THREADS, A));
+        const uint32_t nb = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(((uint64_t)A.tile_cap + 3) / 4, (uint64_t)o->n_cus * 16));
+        NGZ_STAGE_HIP(o, o->launch(use_float ? k_fj_size<true> : k_fj_size<false>, nb, FJ_THREADS, A));
     }
-    NGZ_STAGE_HIP(o, hipEventRecord(o->ev[1], st));
-    if (NS) NGZ_STAGE_HIP(o, launch(k_fj_set_len, blocks(NS), FJ_THREADS, A));
-    NGZ_STAGE_HIP(o, launch(k_fj_dgram_len, blocks(D), FJ_THREADS, A));
-    NGZ_STAGE_HIP(o, hipcub::DeviceScan::ExclusiveSum(o->d_scan_tmp.p, scan_b, (const unsigned long long *)A.dlen, A.offs, (int)(D + 1), st));
-    ++o->launches;
-    NGZ_STAGE_HIP(o, hipEventRecord(o->ev[2], st));
-    unsigned long long *hb = o->h_back.p;
-    hb[C_COUNT + 1] = 0;
-    NGZ_STAGE_HIP(o, hipMemcpyAsync(hb, o->d_counters.p, C_COUNT * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    NGZ_STAGE_HIP(o, hipMemcpyAsync(hb + C_COUNT, A.offs + D, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    if (NS) NGZ_STAGE_HIP(o, hipMemcpyAsync(hb + C_COUNT + 1, A.tile0 + NS, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    NGZ_STAGE_HIP(o, hipStreamSynchronize(st));
-    NGZ_STAGE_HIP(o, hipEventElapsedTime(&o->size_ms, o->ev[0], o->ev[1]));
-    NGZ_STAGE_HIP(o, hipEventElapsedTime(&o->offsets_ms, o->ev[1], o->ev[2]));
-    if (hb[C_ERR] & (ERR_SETS | ERR_TILES)) return ngzs::fail_sets(o);
-    if (hb[C_ERR] & ERR_VLEN) return ngzs::fail(o, NGZ_E_INVALID, "a variable-length cell outside the batch input");
-    const unsigned long long total = hb[C_COUNT];
-    const uint32_t n_tiles = (uint32_t)hb[C_COUNT + 1];
-    if (n_tiles > tile_cap) return ngzs::fail_sets(o);
-    if (o->d_bytes.ensure(total + NGZ_OUTPUT_GUARD + 16)) return ngzs::fail(o, NGZ_E_NOMEM, "flow JSON bytes");
-    A.out = o->d_bytes.p;
-    A.total = total;
+    uint32_t n_tiles = 0;
+    if (int rc = run_offsets<FStream>(o, A, &n_tiles)) return rc;
+    const unsigned long long total = A.total;
+    hipStream_t st = o->st;
     NGZ_STAGE_HIP(o, hipMemsetAsync(A.out + total, 0xA5, NGZ_OUTPUT_GUARD, st));
     if (total) {
         NGZ_STAGE_HIP(o, hipEventRecord(o->ev[0], st));
-        NGZ_STAGE_HIP(o, launch(k_fj_glue_dgrams, blocks(D), FJ_THREADS, A));
-        if (NS) NGZ_STAGE_HIP(o, launch(k_fj_glue_sets, blocks(NS), FJ_THREADS, A));
+        NGZ_STAGE_HIP(o, o->launch(k_fj_glue_dgrams, blocks(D), FJ_THREADS, A));
+        if (NS) NGZ_STAGE_HIP(o, o->launch(k_fj_glue_sets, blocks(NS), FJ_THREADS, A));
         if (n_tiles) {
             const uint32_t nb = (uint32_t)std::min<uint64_t>(n_tiles, (uint64_t)o->n_cus * 16);
-            NGZ_STAGE_HIP(o, launch(use_float ? k_fj_pack<JAcc, true> : k_fj_pack<JAcc, false>, nb, 64u, A, n_tiles));
+            NGZ_STAGE_HIP(o, o->launch(use_float ? k_fj_pack<JAcc, true> : k_fj_pack<JAcc, false>, nb, 64u, A, n_tiles));
         }
         NGZ_STAGE_HIP(o, hipEventRecord(o->ev[3], st));
     }
-    NGZ_STAGE_HIP(o, hipMemcpyAsync(hb + C_COUNT, o->d_counters.p, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    NGZ_STAGE_HIP(o, hipStreamSynchronize(st));
+    if (int rc = read_errors(o)) return rc;
     if (total) NGZ_STAGE_HIP(o, hipEventElapsedTime(&o->pack_ms, o->ev[0], o->ev[3]));
-    if (hb[C_COUNT] & ERR_VLEN) return ngzs::fail(o, NGZ_E_INVALID, "a variable-length cell outside the batch input");
-    o->have = true;
-    o->n_dgrams = D;
-    o->n_bytes = total;
+    if (int rc = finish(o, D, total)) return rc;
+    const unsigned long long *hb = o->h_back.p;
     if (stats) *stats = ngz_flow_json_stats{hb[C_LINES], total, hb[C_TEMPLATE], hb[C_FLOAT], hb[C_NOT_OK]};
     return NGZ_OK;
 }
 
 int ngz_flow_json_result(ngz_flow_json *o, const uint8_t **bytes, const uint64_t **offsets, const uint8_t **how, uint64_t *n_dgrams,
                          uint64_t *n_bytes) {
-    if (!o) return NGZ_E_INVALID;
-    if (!o->have) return ngzs::fail(o, NGZ_E_INVALID, "no encode to read");
-    if (bytes) *bytes = o->n_dgrams ? o->d_bytes.p : nullptr;
-    if (offsets) *offsets = o->n_dgrams ? (const uint64_t *)o->d_offs.p : nullptr;
-    if (how) *how = o->n_dgrams ? o->d_how.p : nullptr;
-    if (n_dgrams) *n_dgrams = o->n_dgrams;
-    if (n_bytes) *n_bytes = o->n_bytes;
-    return NGZ_OK;
+    return ngzms::result(o, bytes, offsets, how, n_dgrams, n_bytes);
 }
 
 int ngz_flow_json_to_host(ngz_flow_json *o, uint8_t *bytes, uint64_t bytes_cap, uint64_t *offsets, uint64_t offsets_cap, uint8_t *how,
                           uint64_t how_cap) {
-    if (!o) return NGZ_E_INVALID;
-    if (!o->have) return ngzs::fail(o, NGZ_E_INVALID, "no encode to read");
-    if ((bytes && bytes_cap < o->n_bytes) || (offsets && offsets_cap < o->n_dgrams + 1) || (how && how_cap < o->n_dgrams))
-        return ngzs::fail(o, NGZ_E_INVALID, "a buffer smaller than the result");
-    if (!o->n_dgrams) {
-        if (offsets && offsets_cap) offsets[0] = 0;
-        return NGZ_OK;
-    }
-    NGZ_STAGE_HIP(o, hipSetDevice(o->device));
-    if (bytes) {
-        const uint64_t n = bytes_cap >= o->n_bytes + NGZ_OUTPUT_GUARD ? o->n_bytes + NGZ_OUTPUT_GUARD : o->n_bytes;
-        if (n) NGZ_STAGE_HIP(o, hipMemcpy(bytes, o->d_bytes.p, n, hipMemcpyDeviceToHost));
-    }
-    if (offsets) NGZ_STAGE_HIP(o, hipMemcpy(offsets, o->d_offs.p, (o->n_dgrams + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    if (how) NGZ_STAGE_HIP(o, hipMemcpy(how, o->d_how.p, o->n_dgrams, hipMemcpyDeviceToHost));
-    return NGZ_OK;
+    return ngzms::to_host(o, bytes, bytes_cap, offsets, offsets_cap, how, how_cap);
 }
 
 int ngz_flow_json_last_timing(ngz_flow_json *o, float *size_ms, float *offsets_ms, float *pack_ms) {

@@ -1,8 +1,9 @@
 // The Avro writers and encoders of the output stages (ngz_output.hip over decoded columns,
-// ngz_agg_output.hip over aggregated rows; included by those units only): a counting and a storing
-// writer, one set of encoders templated on them, so that a size pass and a pack pass run the same
-// code and the sizes are the packed bytes by construction, and the pack pass's LDS image and copy-out
-// over one wave's rows.  Device only, header only.
+// ngz_agg_output.hip over aggregated rows): a counting and a storing writer, one set of encoders
+// templated on them, so that a size pass and a pack pass run the same code and the sizes are the packed
+// bytes by construction, and the pack pass's LDS image and copy-out over one wave's rows, which the JSON
+// and wire stages pack with too (ngz_agg_json.hip and ngz_flow_json.hip through ngz_json_dev.h,
+// ngz_wire.hip).  Included by those five units only.  Device only, header only.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -184,6 +185,16 @@ __device__ __forceinline__ void encode_value(W &w, const S &src, const Cell &c) 
     }
 }
 
+// The wave's image of `len` bytes at img + mis out to dst, mis = dst mod 16: the ragged head and the tail by
+// bytes (at most 15 each, a lane a byte), the 16-byte aligned middle in 16-byte stores
+__device__ __forceinline__ void copy_out(const uint8_t *img, uint32_t mis, uint8_t *dst, uint32_t len, uint32_t lane) {
+    const uint32_t head = min(len, (16u - mis) & 15u);
+    const uint32_t n16 = (len - head) / 16u, tail0 = head + 16u * n16;
+    if (lane < head) dst[lane] = img[mis + lane];
+    if (lane < len - tail0) dst[tail0 + lane] = img[mis + tail0 + lane];
+    for (uint32_t i = lane; i < n16; i += 64u) *(uint4 *)(dst + head + 16u * i) = *(const uint4 *)(img + mis + head + 16u * i);
+}
+
 // The pack pass over one wave's tile of at most 64 consecutive rows.  Lane l < nt owns row l, whose datum
 // fills out[base + rel0, base + rel1) (the scanned offsets, relative to the tile's first).  The wave encodes
 // the rows [g0, g1) whose bytes fit the image together into `img`, IMG + 16 bytes of LDS laid out like
@@ -219,14 +230,7 @@ __device__ __forceinline__ void pack_tile(uint32_t lane, uint32_t nt, unsigned l
         }
         __threadfence_block();
         __builtin_amdgcn_wave_barrier();
-        if (base + gb + len <= total) {
-            const uint32_t head = min(len, (16u - mis) & 15u);  // ragged head, then tail, then the aligned middle
-            const uint32_t n16 = (len - head) / 16u, tail0 = head + 16u * n16;
-            if (lane < head) dst[lane] = img[mis + lane];
-            if (lane < len - tail0) dst[tail0 + lane] = img[mis + tail0 + lane];
-            for (uint32_t i = lane; i < n16; i += 64u)
-                *(uint4 *)(dst + head + 16u * i) = *(const uint4 *)(img + mis + head + 16u * i);
-        }
+        if (base + gb + len <= total) copy_out(img, mis, dst, len, lane);
         __threadfence_block();
         __builtin_amdgcn_wave_barrier();
         g0 = g1;

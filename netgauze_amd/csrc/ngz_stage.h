@@ -1,6 +1,7 @@
-// What the post-decode stages share (ngz_renorm.hip, ngz_enrich.hip, ngz_options.hip, ngz_output.hip; included by
-// those units only): the device helpers of their set and row kernels, and the host scaffold of a
-// stage handle.  Header only.
+// What the post-decode stages share (ngz_renorm.hip, ngz_enrich.hip, ngz_options.hip, ngz_output.hip,
+// ngz_agg_output.hip, ngz_agg_json.hip, and through ngz_msg_stream.h ngz_flow_json.hip and ngz_wire.hip; included
+// by those only): the device helpers of their set and row kernels, and the host scaffold of a stage handle.
+// Header only.
 #pragma once
 #include <hip/hip_runtime.h>
 

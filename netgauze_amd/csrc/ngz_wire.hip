@@ -1,19 +1,20 @@
 // The Encoder half of the codec (include/ngz/flow_wire.h): the IPFIX / NetFlow v9 message of every OK
 // datagram of a batch, written again from the decoded columns.  The mirror of the staged decode: host-endian
 // SoA columns in, big-endian AoS records out, interleaved with message and set headers in stream order.
-// The bookkeeping is ngz_flow_json.hip's: the whole output is one byte stream, every byte a record's or
-// glue (message head, set header, NFv9 set padding), and the unit of work is a tile, at most 64 consecutive
-// records of one data set: consecutive rows of one slot's columns and consecutive bytes of the output.
-// Per encode the host lists every slot's fields as items (column, operation, wire length, offset in the
-// record), uploads the plan in one copy, and runs, whatever the number of slots,
-//   k_w_dgrams      one thread per datagram: written, not OK, or left to the host for its template sets,
-//   k_w_sets        one thread per data set: its datagram's range of sets; an unwritable template's datagram,
-//   k_w_tiles       one thread per data set: its tiles, ceil(n / 64), if its datagram is written,
-//   a hipcub exclusive scan and k_w_fill: the tile table, and every tile's bytes where the slot's records
+// The bookkeeping is ngz_msg_stream.h's, shared with ngz_flow_json.hip: the whole output is one byte stream,
+// every byte a record's or glue (message head, set header, NFv9 set padding), and the unit of work is a tile,
+// at most 64 consecutive records of one data set: consecutive rows of one slot's columns and consecutive
+// bytes of the output.  Per encode the host lists every slot's fields as items (column, operation, wire
+// length, offset in the record), uploads the plan in one copy, and runs, whatever the number of slots, the
+// shared passes (WStream below says what is this stage's in them) around its own, the k_w_ ones:
+//   k_dgrams        one thread per datagram: written, not OK, or left to the host for its template sets,
+//   k_sets          one thread per data set: its datagram's range of sets; an unwritable template's datagram,
+//   k_tiles         one thread per data set: its tiles, ceil(n / 64), if its datagram is written,
+//   a hipcub exclusive scan and k_fill: the tile table, and every tile's bytes where the slot's records
 //                   have one length (records x rec_len: no pass over rows),
 //   k_w_size        only with records of variable-length templates: a wave per such tile, a lane per record
 //                   through the counting writer,
-//   k_w_set_len, k_w_dgram_len, a hipcub exclusive scan: the u64 offsets and the stats,
+//   k_set_len, k_dgram_len, a hipcub exclusive scan: the u64 offsets and the stats,
 //   k_w_glue_dgrams / k_w_glue_sets  message heads, set headers and padding by bytes; every set's and
 //                   tile's output offset,
 //   k_w_pack_fixed  the transpose: a wave per tile of a fixed-length slot.  Lane l loads row l's cell of
@@ -26,7 +27,6 @@
 // put_field below is the one statement of the field bytes: the host specification (ngz_dgram_wire), the
 // counting pass and k_w_pack_rows run it; k_w_pack_fixed is written apart from it and checked against it.
 #include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
 
 #include <algorithm>
 #include <cstring>
@@ -35,17 +35,18 @@
 
 #include "ngz/flow_wire.h"
 #include "ngz_host.h"
+#include "ngz_msg_stream.h"
 #include "ngz_output_enc.h"
-#include "ngz_stage.h"
 
 namespace {
 
-constexpr uint32_t W_THREADS = 256;
-constexpr uint32_t W_TILE = 64;
+using namespace ngzms;
+using ngzrow::align256;
+
+constexpr uint32_t W_THREADS = THREADS;
 // A wave's record image: 64 records of 256 bytes, and 16 of slack for the output's misalignment
 constexpr uint32_t W_IMG = 16384;
-constexpr uint32_t ERR_SETS = 1, ERR_VLEN = 2, ERR_TILES = 4;
-constexpr uint32_t C_ERR = 0, C_WIRE = 1, C_TEMPLATE = 2, C_UNWRITABLE = 3, C_NOT_OK = 4, C_COUNT = 5;
+constexpr uint32_t C_WIRE = 1, C_TEMPLATE = 2, C_UNWRITABLE = 3, C_NOT_OK = 4;  // ngz_wire_stats' order
 
 enum : uint8_t {
     OP_INT,     // the low `len` bytes of the cell's integer, big-endian (len may exceed the column: tcpControlBits)
@@ -71,27 +72,10 @@ struct WSlot {
     uint32_t rec_len, tid;
     uint32_t unwritable, proto;
 };
-struct WTile {
-    uint32_t set, first;
-};
-struct WArgs {  // passed by value
+struct WArgs : Layout {  // passed by value
     const WSlot *slots;
     const WItem *items;
-    const uint32_t *host_dgrams;  // the datagrams with (options) template sets, ascending
-    const ngz_set_info *sets;
-    const ngz_dgram_hdr *hdr;
-    const uint8_t *in;  // the batch input
-    unsigned long long in_size;
-    uint32_t n_host, n_sets, n_dgrams, n_slots, tile_cap, align4;
-    uint8_t *how;
-    uint32_t *dset0, *dset1;
-    uint32_t *ntiles, *tile0;  // per set, and one more: tile0[n_sets] is the number of tiles
-    WTile *tiles;
-    uint32_t *tile_bytes;
-    unsigned long long *tile_off, *set_len, *set_off, *dlen, *offs;
-    uint8_t *out;
-    unsigned long long total;
-    unsigned long long *counters;
+    uint32_t align4;
 };
 
 // The writers: counting and storing (nothing is stored at or past `end`)
@@ -109,7 +93,7 @@ struct WPut {
 
 __host__ __device__ inline uint64_t ld_cell(const uint8_t *p, uint32_t w) {  // device: p aligned to w
 #ifdef __HIP_DEVICE_COMPILE__
-    return w == 8 ? *(const uint64_t *)p : w == 4 ? *(const uint32_t *)p : w == 2 ? *(const uint16_t *)p : *p;
+    return ngzms::ld_cell(p, w);
 #else
     uint64_t v = 0;
     for (uint32_t i = 0; i < w; ++i) v |= (uint64_t)p[i] << (8 * i);
@@ -193,10 +177,6 @@ __host__ __device__ inline uint32_t set_pad(uint32_t proto, uint32_t align4, uns
     return proto == 9 && align4 ? (uint32_t)(len % 4) : 0u;
 }
 
-__device__ __forceinline__ bool set_ok(const WArgs &A, const ngz_set_info &si) {
-    return si.dgram < A.n_dgrams && si.slot < A.n_slots && (!si.n || (uint64_t)si.rec0 + si.n <= A.slots[si.slot].n_rows);
-}
-
 // Row `row` of slot S as a record
 template <class W>
 __device__ __forceinline__ void put_record(const WArgs &A, const WSlot &S, uint32_t row, W &w, uint32_t *err) {
@@ -209,113 +189,38 @@ __device__ __forceinline__ void put_record(const WArgs &A, const WSlot &S, uint3
 // ---------------------------------------------------------------------------------------------
 // kernels
 // ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(W_THREADS) void k_w_dgrams(const WArgs A) {
-    const uint32_t d = blockIdx.x * W_THREADS + threadIdx.x;
-    if (d >= A.n_dgrams) return;
-    uint8_t how = A.hdr[d].status == NGZ_DG_OK ? NGZ_WIRE_WIRE : NGZ_WIRE_NONE;
-    uint32_t lo = 0, hi = A.n_host;
-    while (lo < hi) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (A.host_dgrams[mid] < d) lo = mid + 1;
-        else hi = mid;
+// What is this stage's in the shared passes (ngz_msg_stream.h)
+struct WStream {
+    using Args = WArgs;
+    static __device__ __forceinline__ int sets_how(const WSlot &S, const uint8_t &how) { return S.unwritable && how != HOW_NONE ? NGZ_WIRE_UNWRITABLE : -1; }
+    // SK_ROWS_VLEN (rec_len 0): k_w_size stores the bytes after this
+    static __device__ __forceinline__ void fill_tile(const WArgs &A, const WSlot &S, uint32_t n, uint32_t t, uint32_t first) {
+        A.tile_bytes[t] = min(TILE, n - first) * S.rec_len;
     }
-    if (how == NGZ_WIRE_WIRE && lo < A.n_host && A.host_dgrams[lo] == d) how = NGZ_WIRE_HOST;
-    A.how[d] = how;
-    A.dset0[d] = A.dset1[d] = 0;
-}
-
-__global__ __launch_bounds__(W_THREADS) void k_w_sets(const WArgs A) {
-    const uint32_t s = blockIdx.x * W_THREADS + threadIdx.x;
-    if (s >= A.n_sets) return;
-    const ngz_set_info si = A.sets[s];
-    if (!set_ok(A, si)) {
-        atomicOr((unsigned int *)&A.counters[C_ERR], ERR_SETS);
-        return;
+    // Header, tiles, padding: the padding is part of the length the header carries
+    static __device__ __forceinline__ unsigned long long set_len(const WArgs &A, const ngz_set_info &si, unsigned long long tiles) {
+        const unsigned long long len = 4 + tiles;
+        return len + set_pad(A.slots[si.slot].proto, A.align4, len);
     }
-    if (s == 0 || A.sets[s - 1].dgram != si.dgram) A.dset0[si.dgram] = s;  // the sets are in stream order
-    if (s + 1 == A.n_sets || A.sets[s + 1].dgram != si.dgram) A.dset1[si.dgram] = s + 1;
-    // several sets of a datagram may store the same value; k_w_dgrams ran before
-    if (A.slots[si.slot].unwritable && A.how[si.dgram] != NGZ_WIRE_NONE) A.how[si.dgram] = NGZ_WIRE_UNWRITABLE;
-}
-
-__global__ __launch_bounds__(W_THREADS) void k_w_tiles(const WArgs A) {
-    const uint32_t s = blockIdx.x * W_THREADS + threadIdx.x;
-    if (s > A.n_sets) return;
-    uint32_t n = 0;
-    if (s < A.n_sets) {
-        const ngz_set_info si = A.sets[s];
-        if (set_ok(A, si) && A.how[si.dgram] == NGZ_WIRE_WIRE) n = (si.n + W_TILE - 1) / W_TILE;
+    static __device__ __forceinline__ unsigned long long dgram_frame(const WArgs &, const ngz_dgram_hdr &h, uint32_t) { return head_len(h); }
+    static __device__ __forceinline__ uint32_t counter(const WArgs &, uint32_t, uint8_t how) {  // C_WIRE + this
+        return how == HOW_WRITTEN ? 0u : how == HOW_HOST ? 1u : how == NGZ_WIRE_UNWRITABLE ? 2u : 3u;
     }
-    A.ntiles[s] = n;  // ntiles[n_sets] = 0: the scan's last item
-}
-
-__global__ __launch_bounds__(W_THREADS) void k_w_fill(const WArgs A) {
-    const uint32_t s = blockIdx.x * W_THREADS + threadIdx.x;
-    if (s >= A.n_sets) return;
-    const uint32_t t0 = A.tile0[s], n = A.ntiles[s];
-    if (!n) return;
-    const ngz_set_info si = A.sets[s];
-    const uint32_t rec_len = A.slots[si.slot].rec_len;  // SK_ROWS_VLEN: k_w_size stores the bytes after this
-    for (uint32_t t = 0; t < n; ++t) {
-        if (t0 + t >= A.tile_cap || t0 + t < t0) {
-            atomicOr((unsigned int *)&A.counters[C_ERR], ERR_TILES);
-            break;
-        }
-        A.tiles[t0 + t] = WTile{s, t * W_TILE};
-        A.tile_bytes[t0 + t] = min(W_TILE, si.n - t * W_TILE) * rec_len;
-    }
-}
+};
 
 __global__ __launch_bounds__(W_THREADS) void k_w_size(const WArgs A) {
     const uint32_t lane = threadIdx.x & 63u, n_tiles = min(A.tile0[A.n_sets], A.tile_cap);
     uint32_t err = 0;
     for (uint32_t t = blockIdx.x * (W_THREADS / 64u) + (threadIdx.x >> 6); t < n_tiles; t += gridDim.x * (W_THREADS / 64u)) {
-        const WTile tl = A.tiles[t];
-        const ngz_set_info si = A.sets[tl.set];
-        const WSlot &S = A.slots[si.slot];
+        const TileRows tr = tile_rows(A, t);
+        const WSlot &S = A.slots[tr.si.slot];
         if (S.kind != SK_ROWS_VLEN) continue;
-        const uint32_t cnt = min(W_TILE, si.n - tl.first);
         WCount w;
-        if (lane < cnt) put_record(A, S, si.rec0 + tl.first + lane, w, &err);
+        if (lane < tr.cnt) put_record(A, S, tr.row0 + lane, w, &err);
         const uint64_t sum = ngzs::wave_sum(w.n);
         if (lane == 0) A.tile_bytes[t] = (uint32_t)sum;
     }
     if (err) atomicOr((unsigned int *)&A.counters[C_ERR], err);
-}
-
-// Header, tiles, padding: the padding is part of the length the header carries
-__global__ __launch_bounds__(W_THREADS) void k_w_set_len(const WArgs A) {
-    const uint32_t s = blockIdx.x * W_THREADS + threadIdx.x;
-    if (s >= A.n_sets) return;
-    const ngz_set_info si = A.sets[s];
-    unsigned long long len = 0;
-    if (set_ok(A, si) && A.how[si.dgram] == NGZ_WIRE_WIRE) {
-        len = 4;
-        const uint32_t t1 = min(A.tile0[s + 1], A.tile_cap);
-        for (uint32_t t = A.tile0[s]; t < t1; ++t) len += A.tile_bytes[t];
-        len += set_pad(A.slots[si.slot].proto, A.align4, len);
-    }
-    A.set_len[s] = len;
-}
-
-__global__ __launch_bounds__(W_THREADS) void k_w_dgram_len(const WArgs A) {
-    __shared__ unsigned long long acc[4];
-    const uint32_t d = blockIdx.x * W_THREADS + threadIdx.x;
-    uint64_t c[4] = {0, 0, 0, 0};  // written, left for templates, unwritable, not OK
-    if (d < A.n_dgrams) {
-        unsigned long long len = 0;
-        const uint8_t how = A.how[d];
-        if (how == NGZ_WIRE_WIRE) {
-            len = head_len(A.hdr[d]);
-            const uint32_t s0 = A.dset0[d], s1 = min(A.dset1[d], A.n_sets);
-            for (uint32_t s = s0; s < s1; ++s) len += A.set_len[s];
-        }
-        c[how == NGZ_WIRE_WIRE ? 0 : how == NGZ_WIRE_HOST ? 1 : how == NGZ_WIRE_UNWRITABLE ? 2 : 3] = 1;
-        A.dlen[d] = len;
-        if (d == 0) A.dlen[A.n_dgrams] = 0;  // the scan's last item
-    }
-    unsigned long long *const dst[4] = {&A.counters[C_WIRE], &A.counters[C_TEMPLATE], &A.counters[C_UNWRITABLE], &A.counters[C_NOT_OK]};
-    ngzs::block_add<4>(acc, c, dst);
 }
 
 // The message head; where each of the datagram's sets starts
@@ -372,19 +277,18 @@ __global__ __launch_bounds__(64) void k_w_pack_fixed(const WArgs A, const uint32
     __shared__ __attribute__((aligned(16))) uint8_t img[W_IMG + 16];
     const uint32_t lane = threadIdx.x;
     for (uint32_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
-        const WTile tl = A.tiles[t];
-        const ngz_set_info si = A.sets[tl.set];
-        const WSlot &S = A.slots[si.slot];
+        const TileRows tr = tile_rows(A, t);
+        const WSlot &S = A.slots[tr.si.slot];
         if (S.kind != SK_FIXED) continue;
-        const uint32_t cnt = min(W_TILE, si.n - tl.first), rl = S.rec_len;
-        const uint32_t rpg = min(W_TILE, W_IMG / rl);  // records an image holds: rl <= W_IMG
+        const uint32_t cnt = tr.cnt, rl = S.rec_len;
+        const uint32_t rpg = min(TILE, W_IMG / rl);  // records an image holds: rl <= W_IMG
         for (uint32_t g0 = 0; g0 < cnt; g0 += rpg) {
             const uint32_t gc = min(rpg, cnt - g0), len = gc * rl;
             const unsigned long long o = A.tile_off[t] + (unsigned long long)g0 * rl;
             uint8_t *const dst = A.out + o;
             const uint32_t mis = (uint32_t)((uintptr_t)dst & 15u);
             if (lane < gc) {
-                const uint64_t row = (uint64_t)si.rec0 + tl.first + g0 + lane;
+                const uint64_t row = (uint64_t)tr.si.rec0 + tr.first + g0 + lane;
                 const uint32_t r0 = mis + lane * rl;
                 for (uint32_t i = 0; i < S.n_items; ++i) {
                     const WItem &it = A.items[S.item0 + i];
@@ -416,13 +320,7 @@ __global__ __launch_bounds__(64) void k_w_pack_fixed(const WArgs A, const uint32
             }
             __threadfence_block();
             __builtin_amdgcn_wave_barrier();
-            if (o + len <= A.total) {  // ragged head, then tail, then the aligned middle: pack_tile's copy-out
-                const uint32_t head = min(len, (16u - mis) & 15u);
-                const uint32_t n16 = (len - head) / 16u, tail0 = head + 16u * n16;
-                if (lane < head) dst[lane] = img[mis + lane];
-                if (lane < len - tail0) dst[tail0 + lane] = img[mis + tail0 + lane];
-                for (uint32_t i = lane; i < n16; i += 64u) *(uint4 *)(dst + head + 16u * i) = *(const uint4 *)(img + mis + head + 16u * i);
-            }
+            if (o + len <= A.total) ngzenc::copy_out(img, mis, dst, len, lane);
             __threadfence_block();
             __builtin_amdgcn_wave_barrier();
         }
@@ -435,13 +333,12 @@ __global__ __launch_bounds__(64) void k_w_pack_rows(const WArgs A, const uint32_
     const uint32_t lane = threadIdx.x;
     uint32_t err = 0;
     for (uint32_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
-        const WTile tl = A.tiles[t];
-        const ngz_set_info si = A.sets[tl.set];
-        const WSlot &S = A.slots[si.slot];
+        const TileRows tr = tile_rows(A, t);
+        const WSlot &S = A.slots[tr.si.slot];
         if (S.kind == SK_FIXED) continue;
-        const uint32_t cnt = min(W_TILE, si.n - tl.first), row = si.rec0 + tl.first + lane;
+        const uint32_t row = tr.row0 + lane;
         uint32_t mine = 0;
-        if (lane < cnt) {
+        if (lane < tr.cnt) {
             if (S.kind == SK_ROWS_VLEN) {
                 WCount c;
                 put_record(A, S, row, c, &err);
@@ -450,13 +347,8 @@ __global__ __launch_bounds__(64) void k_w_pack_rows(const WArgs A, const uint32_
                 mine = S.rec_len;
             }
         }
-        uint32_t incl = mine;
-#pragma unroll
-        for (int k = 1; k < 64; k <<= 1) {
-            const uint32_t up = __shfl_up(incl, k, 64);
-            if (lane >= (uint32_t)k) incl += up;
-        }
-        ngzenc::pack_tile<W_IMG, WPut, WPut>(lane, cnt, A.tile_off[t], incl - mine, incl, A.out, A.total, img,
+        const uint32_t incl = wave_incl_scan(mine);
+        ngzenc::pack_tile<W_IMG, WPut, WPut>(lane, tr.cnt, A.tile_off[t], incl - mine, incl, A.out, A.total, img,
                                              [&](auto &w) { put_record(A, S, row, w, &err); });
     }
     if (err) atomicOr((unsigned int *)&A.counters[C_ERR], err);
@@ -468,19 +360,10 @@ __global__ __launch_bounds__(W_THREADS) void k_w_guard(uint8_t *p, uint32_t n) {
 
 }  // namespace
 
-struct ngz_wire : ngzs::Stage {
-    ngz_wire() : Stage(4) {}
-    float size_ms = 0, offsets_ms = 0, glue_ms = 0, pack_ms = 0;
-    int launches = 0;
+struct ngz_wire : ngzms::MsgStage {  // its plan in d_in: slots, items
+    ngz_wire() : MsgStage("wire") {}
+    float glue_ms = 0;
     int align4 = 0;
-    uint64_t n_dgrams = 0, n_bytes = 0;  // the last encode
-    bool have = false;
-    ngzh::DevBuf<uint8_t> d_in, d_how, d_bytes, d_scan_tmp;  // d_in: slots, items, template datagrams
-    ngzh::DevBuf<uint32_t> d_u32;                            // dset0, dset1, ntiles, tile0, tile_bytes
-    ngzh::DevBuf<WTile> d_tiles;
-    ngzh::DevBuf<unsigned long long> d_u64, d_offs, d_counters;  // d_u64: tile_off, set_len, set_off, dlen
-    ngzs::PinnedBuf<uint8_t> h_in;
-    ngzs::PinnedBuf<unsigned long long> h_back;  // the counters, the total, the tiles
 };
 
 namespace {
@@ -552,8 +435,6 @@ bool plan_version(const ngzh::Version &ver, std::vector<WItem> &items, WSlot &ws
     ws.kind = vlen ? SK_ROWS_VLEN : off && off <= W_IMG ? SK_FIXED : SK_ROWS_FIXED;
     return true;
 }
-
-uint32_t blocks(uint64_t items) { return (uint32_t)((items + W_THREADS - 1) / W_THREADS); }
 
 void push_be(std::vector<uint8_t> &o, uint64_t v, uint32_t len) {
     for (uint32_t i = len; i-- > 0;) o.push_back((uint8_t)(v >> (8 * i)));
@@ -721,15 +602,7 @@ void ngz_wire_destroy(ngz_wire *w) {
     if (!w) return;
     if (w->device_ready) {
         hipSetDevice(w->device);
-        w->d_in.release();
-        w->d_how.release();
-        w->d_bytes.release();
-        w->d_scan_tmp.release();
-        w->d_u32.release();
-        w->d_tiles.release();
-        w->d_u64.release();
-        w->d_offs.release();
-        w->d_counters.release();
+        w->release_device();
     }
     delete w;
 }
@@ -746,15 +619,9 @@ int ngz_wire_set_option(ngz_wire *w, int option, int64_t value) {
 int ngz_wire_encode(ngz_wire *o, ngz_ctx *ctx, const ngz_batch_out *out, ngz_wire_stats *stats, void *hip_stream) {
     if (!o || !ctx || !out) return NGZ_E_INVALID;
     if (stats) memset(stats, 0, sizeof *stats);
-    o->have = false;
-    o->n_dgrams = o->n_bytes = 0;
-    o->launches = 0;
-    o->size_ms = o->offsets_ms = o->glue_ms = o->pack_ms = 0;
-    if (int rc = ngzs::check_ctx(o, ctx)) return rc;
+    o->glue_ms = 0;
+    if (int rc = ngzms::begin(o, ctx, out)) return rc;
     const uint32_t S = out->n_slots, D = out->n_dgrams, NS = out->n_sets;
-    if (!ngzs::slot_table_ok(out) || S != ctx->slot_version.size() || D != ctx->last_in.n)
-        return ngzs::fail(o, NGZ_E_INVALID, "slot table: `out` is not the context's last decode");
-    if (NS && !out->sets) return ngzs::fail(o, NGZ_E_INVALID, "no set table");
     if (!D) {  // no datagram: no kernel
         o->have = true;
         return NGZ_OK;
@@ -767,15 +634,10 @@ int ngz_wire_encode(ngz_wire *o, ngz_ctx *ctx, const ngz_batch_out *out, ngz_wir
     bool any_fixed = false, any_rows = false, any_vlen = false;
     for (uint32_t s = 0; s < S; ++s) {
         const ngz_slot_info &si = out->slots[s];
-        const int32_t vi = ctx->slot_version[s];
-        if (vi < 0 || (size_t)vi >= ctx->versions.size()) return ngzs::fail(o, NGZ_E_INVALID, "slot table: `out` is not the context's last decode");
-        const ngzh::Version &ver = ctx->versions[vi];
-        if (ver.specs.size() > ver.fields.size()) return ngzs::fail(o, NGZ_E_INVALID, "a template without its column layout");
-        // every column starts at a multiple of 16 bytes: a cell is aligned to its width
-        if (si.n_records && (!si.columns || ((uintptr_t)si.columns & 15) || (si.capacity & 15) || si.capacity < si.n_records))
-            return ngzs::fail(o, NGZ_E_LIMIT, "unexpected column block alignment");
+        const ngzh::Version *ver;
+        if (int rc = ngzms::slot_version(o, ctx, out, s, &ver)) return rc;
         std::string why;
-        if (!plan_version(ver, items, slots[s], &why)) return ngzs::fail(o, NGZ_E_LIMIT, why);
+        if (!plan_version(*ver, items, slots[s], &why)) return ngzs::fail(o, NGZ_E_LIMIT, why);
         WSlot &ws = slots[s];
         ws.n_rows = si.n_records;
         for (uint32_t i = 0; i < ws.n_items; ++i)
@@ -787,160 +649,55 @@ int ngz_wire_encode(ngz_wire *o, ngz_ctx *ctx, const ngz_batch_out *out, ngz_wir
             any_vlen = any_vlen || ws.kind == SK_ROWS_VLEN;
         }
     }
-    std::vector<uint32_t> host_dgrams;  // (datagram, set position) order: ascending
-    for (const ngzh::TemplateSetJson &t : ctx->tmpl_sets)
-        if (host_dgrams.empty() || host_dgrams.back() != t.dgram) host_dgrams.push_back(t.dgram);
-    const uint64_t tile_cap = n_records / W_TILE + NS + 1;  // a set's last tile may be short
-    if (tile_cap >> 31) return ngzs::fail(o, NGZ_E_LIMIT, "batch too large");
-
-    auto align256 = [](uint64_t n) { return (n + 255) & ~255ull; };
-    const uint64_t items_at = align256(slots.size() * sizeof(WSlot)), host_at = items_at + align256(items.size() * sizeof(WItem));
-    const uint64_t in_bytes = host_at + align256(host_dgrams.size() * sizeof(uint32_t)) + 256;
-    if (int rc = ngzs::device_init(o)) return rc;
-    NGZ_STAGE_HIP(o, hipSetDevice(o->device));
-    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
-    size_t scan_a = 0, scan_b = 0;
-    if (hipcub::DeviceScan::ExclusiveSum(nullptr, scan_a, (const uint32_t *)nullptr, (uint32_t *)nullptr, (int)(NS + 1), st) != hipSuccess ||
-        hipcub::DeviceScan::ExclusiveSum(nullptr, scan_b, (const unsigned long long *)nullptr, (unsigned long long *)nullptr, (int)(D + 1), st) !=
-            hipSuccess)
-        return ngzs::fail(o, NGZ_E_DEVICE, "scan temp size");
-    const size_t scan_bytes = std::max(scan_a, scan_b);
-    const uint64_t n_u32 = 2ull * D + 2ull * (NS + 1) + tile_cap, n_u64 = tile_cap + 2ull * NS + D + 1;
-    if (o->h_in.reserve(in_bytes) || o->d_in.ensure(in_bytes) || o->d_how.ensure(D) || o->d_u32.ensure(n_u32) || o->d_tiles.ensure(tile_cap) ||
-        o->d_u64.ensure(n_u64) || o->d_offs.ensure(D + 1) || o->d_counters.ensure(C_COUNT) || o->d_scan_tmp.ensure(scan_bytes + 1) ||
-        o->h_back.reserve(C_COUNT + 2))
-        return ngzs::fail(o, NGZ_E_NOMEM, "wire buffers");
+    const uint64_t items_at = align256(slots.size() * sizeof(WSlot)), plan_bytes = items_at + align256(items.size() * sizeof(WItem));
+    WArgs A{};
+    if (int rc = carve(o, ctx, out, hip_stream, plan_bytes, n_records, &A)) return rc;
     uint8_t *h = o->h_in.p;
-    memset(h, 0, in_bytes);
     if (S) memcpy(h, slots.data(), slots.size() * sizeof(WSlot));
     if (!items.empty()) memcpy(h + items_at, items.data(), items.size() * sizeof(WItem));
-    if (!host_dgrams.empty()) memcpy(h + host_at, host_dgrams.data(), host_dgrams.size() * sizeof(uint32_t));
-
-    WArgs A{};
     A.slots = (const WSlot *)o->d_in.p;
     A.items = (const WItem *)(o->d_in.p + items_at);
-    A.host_dgrams = (const uint32_t *)(o->d_in.p + host_at);
-    A.n_host = (uint32_t)host_dgrams.size();
-    A.sets = out->sets;
-    A.hdr = out->dgrams;
-    A.in = ctx->last_in.bytes;
-    A.in_size = ctx->last_in.bytes_size;
-    A.n_sets = NS;
-    A.n_dgrams = D;
-    A.n_slots = S;
-    A.tile_cap = (uint32_t)tile_cap;
     A.align4 = (uint32_t)o->align4;
-    A.how = o->d_how.p;
-    A.dset0 = o->d_u32.p;
-    A.dset1 = A.dset0 + D;
-    A.ntiles = A.dset1 + D;
-    A.tile0 = A.ntiles + NS + 1;
-    A.tile_bytes = A.tile0 + NS + 1;
-    A.tiles = o->d_tiles.p;
-    A.tile_off = o->d_u64.p;
-    A.set_len = A.tile_off + tile_cap;
-    A.set_off = A.set_len + NS;
-    A.dlen = A.set_off + NS;
-    A.offs = o->d_offs.p;
-    A.counters = o->d_counters.p;
 
-    NGZ_STAGE_HIP(o, hipMemcpyAsync(o->d_in.p, h, in_bytes, hipMemcpyHostToDevice, st));
-    NGZ_STAGE_HIP(o, hipMemsetAsync(o->d_counters.p, 0, C_COUNT * sizeof(unsigned long long), st));
-    NGZ_STAGE_HIP(o, hipEventRecord(o->ev[0], st));
-    auto launch = [&](auto kernel, uint32_t nb, uint32_t threads, auto... args) {
-        hipLaunchKernelGGL(kernel, dim3(nb), dim3(threads), 0, st, args...);
-        ++o->launches;
-        return hipGetLastError();
-    };
-    NGZ_STAGE_HIP(o, launch(k_w_dgrams, blocks(D), W_THREADS, A));
-    if (NS) {
-        NGZ_STAGE_HIP(o, launch(k_w_sets, blocks(NS), W_THREADS, A));
-        NGZ_STAGE_HIP(o, launch(k_w_tiles, blocks((uint64_t)NS + 1), W_THREADS, A));
-        NGZ_STAGE_HIP(o, hipcub::DeviceScan::ExclusiveSum(o->d_scan_tmp.p, scan_a, (const uint32_t *)A.ntiles, A.tile0, (int)(NS + 1), st));
-        ++o->launches;
-        NGZ_STAGE_HIP(o, launch(k_w_fill, blocks(NS), W_THREADS, A));
-        if (any_vlen) {
-            const uint32_t nb = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((tile_cap + 3) / 4, (uint64_t)o->n_cus * 16));
-            NGZ_STAGE_HIP(o, launch(k_w_size, nb, W_THREADS, A));
-        }
+    if (int rc = run_tiles<WStream>(o, A)) return rc;
+    if (NS && any_vlen) {
+        const uint32_t nb = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(((uint64_t)A.tile_cap + 3) / 4, (uint64_t)o->n_cus * 16));
+        NGZ_STAGE_HIP(o, o->launch(k_w_size, nb, W_THREADS, A));
     }
-    NGZ_STAGE_HIP(o, hipEventRecord(o->ev[1], st));
-    if (NS) NGZ_STAGE_HIP(o, launch(k_w_set_len, blocks(NS), W_THREADS, A));
-    NGZ_STAGE_HIP(o, launch(k_w_dgram_len, blocks(D), W_THREADS, A));
-    NGZ_STAGE_HIP(o, hipcub::DeviceScan::ExclusiveSum(o->d_scan_tmp.p, scan_b, (const unsigned long long *)A.dlen, A.offs, (int)(D + 1), st));
-    ++o->launches;
-    NGZ_STAGE_HIP(o, hipEventRecord(o->ev[2], st));
-    unsigned long long *hb = o->h_back.p;
-    hb[C_COUNT + 1] = 0;
-    NGZ_STAGE_HIP(o, hipMemcpyAsync(hb, o->d_counters.p, C_COUNT * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    NGZ_STAGE_HIP(o, hipMemcpyAsync(hb + C_COUNT, A.offs + D, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    if (NS) NGZ_STAGE_HIP(o, hipMemcpyAsync(hb + C_COUNT + 1, A.tile0 + NS, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    NGZ_STAGE_HIP(o, hipStreamSynchronize(st));
-    NGZ_STAGE_HIP(o, hipEventElapsedTime(&o->size_ms, o->ev[0], o->ev[1]));
-    NGZ_STAGE_HIP(o, hipEventElapsedTime(&o->offsets_ms, o->ev[1], o->ev[2]));
-    if (hb[C_ERR] & (ERR_SETS | ERR_TILES)) return ngzs::fail_sets(o);
-    if (hb[C_ERR] & ERR_VLEN) return ngzs::fail(o, NGZ_E_INVALID, "a variable-length cell outside the batch input");
-    const unsigned long long total = hb[C_COUNT];
-    const uint32_t n_tiles = (uint32_t)hb[C_COUNT + 1];
-    if (n_tiles > tile_cap) return ngzs::fail_sets(o);
-    if (o->d_bytes.ensure(total + NGZ_OUTPUT_GUARD + 16)) return ngzs::fail(o, NGZ_E_NOMEM, "wire bytes");
-    A.out = o->d_bytes.p;
-    A.total = total;
-    NGZ_STAGE_HIP(o, launch(k_w_guard, 1u, W_THREADS, A.out + total, (uint32_t)NGZ_OUTPUT_GUARD));
+    uint32_t n_tiles = 0;
+    if (int rc = run_offsets<WStream>(o, A, &n_tiles)) return rc;
+    const unsigned long long total = A.total;
+    hipStream_t st = o->st;
+    NGZ_STAGE_HIP(o, o->launch(k_w_guard, 1u, W_THREADS, A.out + total, (uint32_t)NGZ_OUTPUT_GUARD));
     if (total) {
         NGZ_STAGE_HIP(o, hipEventRecord(o->ev[0], st));
-        NGZ_STAGE_HIP(o, launch(k_w_glue_dgrams, blocks(D), W_THREADS, A));
-        if (NS) NGZ_STAGE_HIP(o, launch(k_w_glue_sets, blocks(NS), W_THREADS, A));
+        NGZ_STAGE_HIP(o, o->launch(k_w_glue_dgrams, blocks(D), W_THREADS, A));
+        if (NS) NGZ_STAGE_HIP(o, o->launch(k_w_glue_sets, blocks(NS), W_THREADS, A));
         NGZ_STAGE_HIP(o, hipEventRecord(o->ev[1], st));
         if (n_tiles) {
             const uint32_t nb = (uint32_t)std::min<uint64_t>(n_tiles, (uint64_t)o->n_cus * 32);
-            if (any_fixed) NGZ_STAGE_HIP(o, launch(k_w_pack_fixed, nb, 64u, A, n_tiles));
-            if (any_rows) NGZ_STAGE_HIP(o, launch(k_w_pack_rows, nb, 64u, A, n_tiles));
+            if (any_fixed) NGZ_STAGE_HIP(o, o->launch(k_w_pack_fixed, nb, 64u, A, n_tiles));
+            if (any_rows) NGZ_STAGE_HIP(o, o->launch(k_w_pack_rows, nb, 64u, A, n_tiles));
         }
         NGZ_STAGE_HIP(o, hipEventRecord(o->ev[3], st));
     }
-    NGZ_STAGE_HIP(o, hipMemcpyAsync(hb + C_COUNT, o->d_counters.p, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    NGZ_STAGE_HIP(o, hipStreamSynchronize(st));
+    if (int rc = read_errors(o)) return rc;
     if (total) {
         NGZ_STAGE_HIP(o, hipEventElapsedTime(&o->glue_ms, o->ev[0], o->ev[1]));
         NGZ_STAGE_HIP(o, hipEventElapsedTime(&o->pack_ms, o->ev[1], o->ev[3]));
     }
-    if (hb[C_COUNT] & ERR_VLEN) return ngzs::fail(o, NGZ_E_INVALID, "a variable-length cell outside the batch input");
-    o->have = true;
-    o->n_dgrams = D;
-    o->n_bytes = total;
+    if (int rc = finish(o, D, total)) return rc;
+    const unsigned long long *hb = o->h_back.p;
     if (stats) *stats = ngz_wire_stats{hb[C_WIRE], total, hb[C_TEMPLATE], hb[C_UNWRITABLE], hb[C_NOT_OK]};
     return NGZ_OK;
 }
 
 int ngz_wire_result(ngz_wire *o, const uint8_t **bytes, const uint64_t **offsets, const uint8_t **how, uint64_t *n_dgrams, uint64_t *n_bytes) {
-    if (!o) return NGZ_E_INVALID;
-    if (!o->have) return ngzs::fail(o, NGZ_E_INVALID, "no encode to read");
-    if (bytes) *bytes = o->n_dgrams ? o->d_bytes.p : nullptr;
-    if (offsets) *offsets = o->n_dgrams ? (const uint64_t *)o->d_offs.p : nullptr;
-    if (how) *how = o->n_dgrams ? o->d_how.p : nullptr;
-    if (n_dgrams) *n_dgrams = o->n_dgrams;
-    if (n_bytes) *n_bytes = o->n_bytes;
-    return NGZ_OK;
+    return ngzms::result(o, bytes, offsets, how, n_dgrams, n_bytes);
 }
 
 int ngz_wire_to_host(ngz_wire *o, uint8_t *bytes, uint64_t bytes_cap, uint64_t *offsets, uint64_t offsets_cap, uint8_t *how, uint64_t how_cap) {
-    if (!o) return NGZ_E_INVALID;
-    if (!o->have) return ngzs::fail(o, NGZ_E_INVALID, "no encode to read");
-    if ((bytes && bytes_cap < o->n_bytes) || (offsets && offsets_cap < o->n_dgrams + 1) || (how && how_cap < o->n_dgrams))
-        return ngzs::fail(o, NGZ_E_INVALID, "a buffer smaller than the result");
-    if (!o->n_dgrams) {
-        if (offsets && offsets_cap) offsets[0] = 0;
-        return NGZ_OK;
-    }
-    NGZ_STAGE_HIP(o, hipSetDevice(o->device));
-    if (bytes) {
-        const uint64_t n = bytes_cap >= o->n_bytes + NGZ_OUTPUT_GUARD ? o->n_bytes + NGZ_OUTPUT_GUARD : o->n_bytes;
-        if (n) NGZ_STAGE_HIP(o, hipMemcpy(bytes, o->d_bytes.p, n, hipMemcpyDeviceToHost));
-    }
-    if (offsets) NGZ_STAGE_HIP(o, hipMemcpy(offsets, o->d_offs.p, (o->n_dgrams + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    if (how) NGZ_STAGE_HIP(o, hipMemcpy(how, o->d_how.p, o->n_dgrams, hipMemcpyDeviceToHost));
-    return NGZ_OK;
+    return ngzms::to_host(o, bytes, bytes_cap, offsets, offsets_cap, how, how_cap);
 }
 
 int ngz_wire_last_timing(ngz_wire *o, float *size_ms, float *offsets_ms, float *glue_ms, float *pack_ms) {

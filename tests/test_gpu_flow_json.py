@@ -50,18 +50,40 @@ def check(dgrams, how, stats=None):
     return batch, fj
 
 
+def tile_edge_dgrams(n):
+    a, b = [rec_a(i) for i in range(n)], [rec_b(i) for i in range(n)]
+    return a, [TEMPLATES, ipfix_msg([ipfix_set(300, b"".join(a))]), ipfix_msg([ipfix_set(300, b"".join(a)), ipfix_set(300, a[0])]),
+               ipfix_msg([ipfix_set(300, b"".join(a)), ipfix_set(302, b"".join(b)), ipfix_set(300, a[-1]), ipfix_set(302, b"".join(b))]),
+               ipfix_msg([])]
+
+
 @pytest.mark.parametrize("n", [1, 63, 64, 65, 129])
 def test_tile_edges(dev, n):
     """Sets of n records around the 64-record tile; two sets of one template; sets alternating between two
     templates; a message of a header alone.  Three templates launch what one template launches."""
-    a, b = [rec_a(i) for i in range(n)], [rec_b(i) for i in range(n)]
-    dgrams = [TEMPLATES, ipfix_msg([ipfix_set(300, b"".join(a))]), ipfix_msg([ipfix_set(300, b"".join(a)), ipfix_set(300, a[0])]),
-              ipfix_msg([ipfix_set(300, b"".join(a)), ipfix_set(302, b"".join(b)), ipfix_set(300, a[-1]), ipfix_set(302, b"".join(b))]),
-              ipfix_msg([])]
+    a, dgrams = tile_edge_dgrams(n)
     _batch, fj = check(dgrams, [HOST, LINE, LINE, LINE, LINE])
     one = [ipfix_msg([ipfix_set(2, tmpl(300, A))])] + dgrams[1:3]
     three = [ipfix_msg([ipfix_set(2, tmpl(300, A) + tmpl(302, B) + tmpl(303, A))])] + dgrams[1:4] + [ipfix_msg([ipfix_set(303, a[0])])]
     assert check(one, [HOST, LINE, LINE])[1].last_launches == check(three, [HOST] + [LINE] * 4)[1].last_launches == fj.last_launches
+
+
+def test_one_handle_across_batches(dev):
+    """One codec and one stage handle over batches of different shape, large, small, large again: after each
+    encode the bytes with their guard, the offsets, `how`, the stats and the launches are those of a fresh
+    handle on the same batch, whatever the handle's buffers held before."""
+    from netgauze_amd.flow import FlowInfoCodec
+    from netgauze_amd.output import FlowJson
+    codec, fj = FlowInfoCodec(0), FlowJson()
+    for n in (129, 1, 129):
+        batch = codec.decode_datagrams(tile_edge_dgrams(n)[1])
+        got, fresh = [], FlowJson()
+        for h in (fj, fresh):
+            st = h.encode(batch)
+            data, offs, how = h.result(guard=True)
+            got.append((data, offs.tolist(), how.tolist(), st, h.last_launches))
+        assert got[0] == got[1], n
+        assert got[0][2] == [HOST, LINE, LINE, LINE, LINE] and got[0][3]["lines"] == 4 and got[0][3]["bytes"] == got[0][1][-1] > 0
 
 
 def fixed_kinds():

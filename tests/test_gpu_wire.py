@@ -120,6 +120,26 @@ def test_launches_do_not_depend_on_slots(dev):
     assert len(synth.CFG3_TEMPLATES) == 8
 
 
+def test_one_handle_across_batches(dev):
+    """One codec and one stage handle over batches of different shape, large, small, large again: after each
+    encode the bytes with their guard, the offsets, `how`, the stats and the launches are those of a fresh
+    handle on the same batch, whatever the handle's buffers held before."""
+    from netgauze_amd.flow import FlowInfoCodec
+    from netgauze_amd.wire import FlowWire
+    codec, fw = FlowInfoCodec(0), FlowWire()
+    streams = {65: t20_stream(65), 1: t20_stream(1)}
+    for per_msg in (65, 1, 65):
+        batch = codec.decode_datagrams(streams[per_msg])
+        got, fresh = [], FlowWire()
+        for h in (fw, fresh):
+            st = h.encode(batch)
+            data, offs, how = h.result(guard=True)
+            got.append((data, offs.tolist(), how.tolist(), st, h.last_launches))
+        assert got[0] == got[1], per_msg
+        assert got[0][2] == [HOST] + [WIRE] * (len(streams[per_msg]) - 1) and got[0][3]["bytes"] == got[0][1][-1] > 0
+        assert got[0][0][:got[0][1][-1]] == b"".join(streams[per_msg][1:])  # the input is what the writer emits (test_identity)
+
+
 # Vectors of kats_packets.CASES the reference parses but does not write back, by wire key: what K.CASES itself
 # does not mark.  For these the test holds the device to the host function only.
 NOT_WRITTEN_BACK = {
